@@ -8,17 +8,25 @@ A step = one pass of the join over the resident batch (stream kernel, mixed-row 
 pass for the rare ambiguous points); with N > 1 GPUs each rank owns its own 1e9-point shard (weak
 scaling) and the step ends with one RCCL all-reduce of the int64[263] counts.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Without a torchrun environment, --gpus N > 1 relaunches itself under torch.distributed.run (before
-touching the GPU) and exits with its status.  Rank 0 prints one JSON line.  `roofline` prices the
-stream kernel against the HBM roofline of its 16 B/point algorithmic input stream (kernel time from
-HIP events on the launch stream); `cpu_baseline` times the CPU restatement (oracle/, "port") on a
+touching the GPU) and exits with its status.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` / `ms_per_step`,
+`config.build_s` (the build side: tessellation + chip table with tile directory and point raster),
+`end_to_end_points_per_s` (one pass including it) and `roofline.achieved`, which prices the stream
+kernel against the HBM roofline of its 16 B/point algorithmic input stream (kernel time from HIP
+events on the launch stream of the timed steps).  --dump-outputs DIR writes what the last timed step
+returned (the per-zone counts, `DIR/counts.npy`, float64); the points are seeded, so two builds run
+with the same arguments are comparable output for output.
+
+--full adds the legs that take runs of their own: `stats` (one synchronous step for the exact-path
+and contains-test counters), `cpu_baseline`, which times the CPU restatement (oracle/, "port") on a
 bounded prefix of the SAME device points, whose counts must equal the GPU's on that prefix
-(`parity`; the bench fails otherwise); `config.build_s` is the build side (tessellation + chip
-table with tile directory and point raster) and `end_to_end_points_per_s` one pass including it.
+(`parity`; the bench fails otherwise), and `roofline.traffic` (rocprofv3 PMC child passes).
 """
 import argparse
 import glob
@@ -46,12 +54,16 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--points-per-gpu", type=float, default=1e9)
     p.add_argument("--res", type=int, default=9)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the stats step, the CPU baseline with its parity check and the PMC passes")
     p.add_argument("--cpu-sample", type=float, default=2e8,
-                   help="prefix of the device points joined by the CPU oracle (0 = skip)")
+                   help="--full: prefix of the device points joined by the CPU oracle (0 = skip)")
     p.add_argument("--cpu-threads", type=int, default=0,
-                   help="threads of the CPU baseline (0 = every CPU this process may run on)")
-    p.add_argument("--pmc", type=int, default=1, help="1: measure HBM traffic with a rocprofv3 PMC child pass")
-    p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+                   help="--full: threads of the CPU baseline (0 = every CPU this process may run on)")
+    p.add_argument("--pmc", type=int, default=1,
+                   help="--full: 1 measures HBM traffic with a rocprofv3 PMC child pass")
     return p.parse_args()
 
 
@@ -154,7 +166,7 @@ def cpu_baseline(chips, res, n_zones, x, y, threads):
 
 
 def pmc_traffic(args):
-    """rocprofv3 PMC child pass (FETCH_SIZE / WRITE_SIZE only, each its own run) on the same launch
+    """rocprofv3 PMC child pass (FETCH_SIZE / WRITE_SIZE only, each its own plain run) on the same launch
     shape; returns HBM bytes per stream-kernel launch with the gfx950 FETCH_SIZE x2 correction."""
     import csv
     import shutil
@@ -168,9 +180,8 @@ def pmc_traffic(args):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = os.path.join(out_dir, counter)
         cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc", "--",
-               sys.executable, os.path.join(ROOT, "bench.py"), "--pmc-child", "--steps", "2", "--warmup", "1",
-               "--points-per-gpu", str(args.points_per_gpu), "--res", str(args.res), "--cpu-sample", "0",
-               "--pmc", "0"]
+               sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+               "--points-per-gpu", str(args.points_per_gpu), "--res", str(args.res)]
         r = subprocess.run(cmd, cwd="/tmp", capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             return None, f"rocprofv3 {counter} failed: {r.stderr[-400:]}"
@@ -190,6 +201,13 @@ def pmc_traffic(args):
     # (MI355X_MICROARCH.md, HBM section): double it.
     traffic = (2.0 * res["FETCH_SIZE"] + res["WRITE_SIZE"]) * 1024.0
     return traffic, res
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each named array as out_dir/<name>.npy in float64 (the counts stay exact: < 2**53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def main():
@@ -263,16 +281,21 @@ def main():
     ctx.set_option("timing", 0)
     elapsed = D.max_over_ranks(elapsed, device=dev)
 
-    # one synchronous step for counters (exact-path rows, contains tests)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"counts": counts.cpu().numpy()})
     ctx.set_option("async", 0)
-    check = ctx.pip_join_count(table, x, y)
-    stats = ctx.last_stats()
-    if args.pmc_child:
-        return
+    stats = None
+    if args.full:
+        # one synchronous step for counters (exact-path rows, contains tests)
+        check = ctx.pip_join_count(table, x, y)
+        last = ctx.last_stats()
+        stats = {"exact_path_rows_per_step": last["exact_path_rows"],
+                 "contains_tests_per_step": last["contains_tests"],
+                 "pairs_per_step": int(check.sum().item())}
     # parity on the full-size workload: the CPU oracle on a prefix of the same device points
     parity = None
     cpu = None
-    if args.cpu_sample > 0 and rank == 0:
+    if args.full and args.cpu_sample > 0 and rank == 0:
         m = int(min(args.cpu_sample, n))
         gpu_prefix = ctx.pip_join_count(table, x[:m], y[:m]).cpu().numpy()
         hx, hy = x[:m].cpu().numpy(), y[:m].cpu().numpy()
@@ -301,7 +324,7 @@ def main():
     k_avg_ms = float(np.mean(kernel_ms)) if len(kernel_ms) else None
     achieved = (BYTES_PER_POINT * n) / (k_avg_ms * 1e-3) / 1e9 if k_avg_ms else None
     traffic, pmc_note = (None, "skipped")
-    if args.pmc and world == 1:
+    if args.full and args.pmc and world == 1:
         try:
             traffic, pmc_note = pmc_traffic(args)
         except Exception as e:  # the measurement is optional; never fail the bench on it
@@ -346,9 +369,7 @@ def main():
                      "pmc": pmc_note},
         "cpu_baseline": cpu,
         "parity": parity,
-        "stats": {"exact_path_rows_per_step": stats["exact_path_rows"],
-                  "contains_tests_per_step": stats["contains_tests"],
-                  "pairs_per_step": int(check.sum().item())},
+        "stats": stats,
     }
     print(json.dumps(line))
     if world > 1:

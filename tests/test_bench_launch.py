@@ -17,6 +17,19 @@ def test_defaults(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.gpus == 1 and a.steps > 0 and a.warmup >= 0 and a.points_per_gpu == 1e9 and a.res == 9
+    assert a.full is False and a.dump_outputs is None  # a plain run: the timed steps and the line only
+
+
+def test_full_and_dump_outputs_options(monkeypatch, tmp_path):
+    import numpy as np
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--full", "--dump-outputs", str(tmp_path / "o")])
+    a = bench.parse()
+    assert a.full is True and a.steps == 7 and a.dump_outputs == str(tmp_path / "o")
+    counts = np.array([0, 3, 2**40 + 1], np.int64)
+    bench.dump_outputs(a.dump_outputs, {"counts": counts})
+    got = np.load(tmp_path / "o" / "counts.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, counts)
 
 
 def test_relaunch_command(monkeypatch):

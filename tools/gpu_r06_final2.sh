@@ -11,7 +11,7 @@ timeout -k 10 700 python3 -u -m pytest tests -m gpu -x -v --timeout 400 --timeou
 echo tests done
 timeout -k 10 200 python3 -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 1
 echo smoke done
-timeout -k 10 300 python3 -u bench.py > $O/bench.txt 2>&1 || exit 1
+timeout -k 10 300 python3 -u bench.py --full > $O/bench.txt 2>&1 || exit 1
 echo bench done
 (cd /tmp && TMPDIR=/tmp timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 -u $R/bench.py --pmc 0 > $O/bench_prof.txt 2>&1) || exit 1
 echo prof done

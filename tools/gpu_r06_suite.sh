@@ -9,6 +9,6 @@ cd $R
 timeout -k 10 900 python3 -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 400 --timeout-method thread > $O/gpu_tests.log 2>&1 || exit 1
 echo tests done
 if [ -z "$NOBENCH" ]; then
-timeout -k 10 400 python3 -u bench.py > $O/bench.txt 2>&1 || exit 1
+timeout -k 10 400 python3 -u bench.py --full > $O/bench.txt 2>&1 || exit 1
 echo bench done
 fi
