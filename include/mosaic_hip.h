@@ -479,6 +479,41 @@ int mosaic_cell_lists_destroy(mosaic_cell_lists* lists);
 /* Device time (HIP events on the calling thread's stream) of the calling thread's last mosaic_polyfill, ms. */
 double mosaic_polyfill_last_ms(void);
 
+/* ---- grid_geometrykring / grid_geometrykloop ---- */
+/* The k-ring (loop = 0) or k-loop (loop = 1) of each geometry's chips (Mosaic.geometryKRing /
+ * geometryKLoop, core/Mosaic.scala:111-144, 211-223; expressions/index/GeometryKRing*.scala,
+ * GeometryKLoop*.scala), on the GPU.  With core = the cells of a geometry's is_core chips, border =
+ * the cells of its other chips and dist(c) = the smallest j with c in kLoop(b, j) for a border cell
+ * b (0 for the border cells):
+ *   k-ring(k) = core + {c : dist(c) <= k}, 0 <= k <= 1000;
+ *   k-loop(k) = {c : dist(c) == k} - core, 1 <= k <= 1000;  any other k: MOSAIC_E_ARG.
+ * H3: a breadth-first search under kRing(., 1); BNG: every border cell's loops 1..k by the
+ * reference's arithmetic (exact at the grid's edge, where a neighbour walk is not).  Row g's cells are
+ * cells[offsets[g] .. offsets[g + 1]) of the result, in Scala 2.12 immutable HashSet iteration order
+ * (equal 32-bit hashes by ascending id); sets of <= 4 cells iterate in insertion order in Scala,
+ * which is not restated, and no reference fixture pins these orders ("order unpinned").
+ * mosaic_chips_kring takes chip columns (the rows of grid_tessellateexplode, or one non-core chip per
+ * point: Mosaic.pointChip): key[i] in [0, n_geoms) names the chip's geometry, duplicate rows are
+ * allowed, a cell given both as core and as border counts as both.  mosaic_geometry_kring is
+ * mosaic_tessellate_gpu(keep_core_geom = 0) followed by it.  Line geometries are not served (the
+ * engine has no lineFill).  status[g]: MOSAIC_POLYFILL_UNSUPPORTED (no cells) for a geometry with a
+ * chip id that is not a valid cell of res; a geometry without chips gives an empty row.
+ * Options: "gk_table_log2" (log2 of the search table's first slot count, 4..30, default 16; the
+ * table grows by rehashing), "gk_max_cells" (slot count past which the call returns
+ * MOSAIC_E_CAPACITY, default 2^27: a safety cap, not a measured one). */
+int mosaic_chips_kring(mosaic_ctx* ctx, int grid, int res, int64_t n_chips, const uint8_t* is_core,
+                       const int64_t* index_id, const int32_t* key, int64_t n_geoms, int k, int loop,
+                       mosaic_cell_lists** out);
+int mosaic_geometry_kring(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const int64_t* geom_parts,
+                          const int64_t* part_rings, const int64_t* ring_offsets, const double* xy, int k, int loop,
+                          mosaic_cell_lists** out);
+/* dist[n_cells] of a geometry k-ring result, cell for cell: -1 for a core cell the search did not
+ * reach within k.  MOSAIC_E_ARG for the lists of mosaic_polyfill, which carry none. */
+int mosaic_cell_lists_export_dist(const mosaic_cell_lists* lists, int32_t* dist);
+/* Device time (HIP events on the calling thread's stream) of the search, sort and offsets of the calling
+ * thread's last mosaic_chips_kring (for mosaic_geometry_kring: without the tessellation), ms. */
+double mosaic_geometry_kring_last_ms(void);
+
 /* getBufferRadius(geometry, res) per geometry (the radius mosaicFill buffers by, core/Mosaic.scala:68):
  * H3 (H3IndexSystem.scala:73-80): the largest distance (degrees) from the centroid of the cell
  * holding the geometry's JTS centroid (its indexToGeometry polygon's JTS centroid) to that polygon's

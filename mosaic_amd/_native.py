@@ -43,7 +43,8 @@ EXPORTS = [
     "mosaic_polyfill_last_ms", "mosaic_ctx_exec", "mosaic_buffer_radius", "mosaic_chip_table_create_arrays",
     "mosaic_intersection_aggregate", "mosaic_thread_release", "mosaic_thread_count", "mosaic_stream_wait_event",
     "mosaic_intersection_aggregate_geometry", "mosaic_isect_geoms_info", "mosaic_isect_geoms_export",
-    "mosaic_isect_geoms_destroy",
+    "mosaic_isect_geoms_destroy", "mosaic_chips_kring", "mosaic_geometry_kring", "mosaic_cell_lists_export_dist",
+    "mosaic_geometry_kring_last_ms",
 ]
 
 GEOM_WKB = 0
@@ -149,6 +150,10 @@ def lib():
         "mosaic_cell_lists_export": ([vp, vp, vp, vp], i32),
         "mosaic_cell_lists_destroy": ([vp], i32),
         "mosaic_polyfill_last_ms": ([], ctypes.c_double),
+        "mosaic_chips_kring": ([vp, i32, i32, i64, vp, vp, vp, i64, i32, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_geometry_kring": ([vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_cell_lists_export_dist": ([vp, vp], i32),
+        "mosaic_geometry_kring_last_ms": ([], ctypes.c_double),
         "mosaic_buffer_radius": ([vp, i32, i32, i64, vp, vp, vp, vp, vp], i32),
         "mosaic_chip_table_create_arrays": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_intersection_aggregate": ([vp, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),

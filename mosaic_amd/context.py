@@ -742,6 +742,102 @@ class MosaicContext:
             return idx, self._serialize(cells)
         return idx, cells
 
+    def _geometry_kring(self, geoms, resolution, k, loop, raw, return_distance=False, return_status=False):
+        res = self.index_system.get_resolution(resolution)
+        grid = self.index_system.grid
+        h = ctypes.c_void_p()
+        if hasattr(geoms, "geom_parts"):  # a PolygonSet
+            N.check(N.lib().mosaic_geometry_kring(self.handle, grid, res, len(geoms), N.ptr(geoms.geom_parts),
+                                                  N.ptr(geoms.part_rings), N.ptr(geoms.ring_offsets),
+                                                  N.ptr(geoms.xy), int(k), int(loop), ctypes.byref(h)))
+        else:
+            if isinstance(geoms, dict):  # chip columns
+                is_core = np.ascontiguousarray(geoms["is_core"], np.uint8)
+                ids = np.ascontiguousarray(geoms["index_id"], np.int64)
+                key = np.ascontiguousarray(geoms["polygon_key"], np.int32)
+                n_geoms = geoms.get("n_geoms")
+                if n_geoms is None:
+                    n_geoms = int(key.max()) + 1 if len(key) else 0
+            else:  # a point column: Mosaic.pointChip, one non-core chip at each point's cell
+                ids = self.grid_pointascellid(geoms, res, raw=True)
+                if _is_torch(ids):
+                    ids = ids.cpu().numpy()
+                ids = np.ascontiguousarray(ids, np.int64)
+                is_core = np.zeros(len(ids), np.uint8)
+                key = np.arange(len(ids), dtype=np.int32)
+                n_geoms = len(ids)
+            N.check(N.lib().mosaic_chips_kring(self.handle, grid, res, len(ids), N.ptr(is_core), N.ptr(ids),
+                                               N.ptr(key), int(n_geoms), int(k), int(loop), ctypes.byref(h)))
+        try:
+            n_rows, n_cells = ctypes.c_int64(0), ctypes.c_int64(0)
+            N.check(N.lib().mosaic_cell_lists_info(h, ctypes.byref(n_rows), ctypes.byref(n_cells)))
+            n = n_rows.value
+            offs = np.zeros(n + 1, np.int64)
+            cells = np.zeros(max(n_cells.value, 1), np.int64)
+            dist = np.zeros(max(n_cells.value, 1), np.int32)
+            status = np.zeros(max(n, 1), np.int32)
+            N.check(N.lib().mosaic_cell_lists_export(h, N.ptr(offs), N.ptr(cells), N.ptr(status)))
+            N.check(N.lib().mosaic_cell_lists_export_dist(h, N.ptr(dist)))
+        finally:
+            N.lib().mosaic_cell_lists_destroy(h)
+        status = status[:n]
+        bad = np.nonzero(status != 0)[0]
+        if len(bad) and not return_status:
+            raise N.MosaicError(N.MOSAIC_E_ARG, f"grid_geometrykring / grid_geometrykloop: rows {bad[:8].tolist()} hold a "
+                                                f"chip id that is not a valid cell of resolution {res}")
+        rows = [cells[offs[g]:offs[g + 1]].copy() for g in range(n)]
+        if not raw and self.index_system.cell_id_type == "string":
+            rows = [list(self._serialize(r)) if len(r) else [] for r in rows]
+        out = (rows,)
+        if return_distance:
+            out += ([dist[offs[g]:offs[g + 1]].copy() for g in range(n)],)
+        if return_status:
+            out += (status,)
+        return out[0] if len(out) == 1 else out
+
+    def grid_geometrykring(self, geoms, resolution, k, raw=False, return_distance=False, return_status=False):
+        """grid_geometrykring(geom, res, k) (python/mosaic/api/functions.py:1184-1207 ->
+        expressions/index/GeometryKRing.scala -> Mosaic.geometryKRing, core/Mosaic.scala:111-116): per
+        geometry, the core cells of its tessellation and the k-rings of its border cells, 0 <= k <=
+        1000, found on this context's GPU as one multi-source search from the border cells
+        (mosaic_geometry_kring / mosaic_chips_kring).
+
+        ``geoms``: a PolygonSet; the chip columns ``tessellate`` / ``grid_tessellateexplode`` return
+        (a dict, optionally with ``n_geoms``; MultiPoint rows are chips sharing a key, one non-core
+        chip per point); or a point column in any form ``grid_pointascellid`` accepts (each row's cell
+        is one border chip, Mosaic.pointChip).  Line geometries are not served (no lineFill here): a
+        point column holding one raises RowPathRequired.
+
+        Returns one array of cells per geometry -- BNG ids as the reference's strings unless raw --
+        in Scala 2.12 immutable HashSet iteration order (the reference returns a Set[Long]; equal
+        hashes by ascending id).  Sets of <= 4 cells iterate in insertion order in Scala, which is
+        not restated, and no reference fixture pins these orders ("order unpinned").
+        return_distance adds, per cell, the smallest loop distance from a border cell (-1: a core
+        cell not reached within k).  A row with a chip id that is not a valid cell of the resolution
+        raises MosaicError, unless return_status, which adds the rows' status array (0 ok, -2 such a
+        row, left empty)."""
+        return self._geometry_kring(geoms, resolution, k, False, raw, return_distance, return_status)
+
+    def grid_geometrykloop(self, geoms, resolution, k, raw=False, return_status=False):
+        """grid_geometrykloop(geom, res, k) (python/mosaic/api/functions.py:1209-1232 ->
+        expressions/index/GeometryKLoop.scala -> Mosaic.geometryKLoop, core/Mosaic.scala:130-144): the
+        cells at loop distance exactly k (1 <= k <= 1000) from the geometry's border cells that are
+        neither core cells nor in the (k - 1)-ring.  Arguments, order and errors as
+        grid_geometrykring; the same search gives every loop 1..k, which is what the KNN iteration
+        (models/knn/GridRingNeighbours.scala:76-99) asks for."""
+        return self._geometry_kring(geoms, resolution, k, True, raw, False, return_status)
+
+    def grid_geometrykringexplode(self, geoms, resolution, k):
+        """grid_geometrykringexplode (python/mosaic/api/functions.py:1234-1257,
+        expressions/index/GeometryKRingExplode.scala): one output row per (geometry, ring cell) --
+        (row index array, cell array), as grid_cellkringexplode."""
+        return self._explode(self.grid_geometrykring(geoms, resolution, k, raw=True))
+
+    def grid_geometrykloopexplode(self, geoms, resolution, k):
+        """grid_geometrykloopexplode (python/mosaic/api/functions.py:1259-1281,
+        expressions/index/GeometryKLoopExplode.scala): one output row per (geometry, loop cell)."""
+        return self._explode(self.grid_geometrykloop(geoms, resolution, k, raw=True))
+
     def _h3_geometry(self, cells, mode):
         ids = np.ascontiguousarray(cells, np.int64)
         n = len(ids)

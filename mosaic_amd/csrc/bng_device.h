@@ -248,6 +248,31 @@ MOSAIC_HD bool is_valid(int64_t id) {
 // kLoop(id, k): the 8k cells of the square loop at distance k, bottom, right, top, left, each
 // side from its first corner, keeping the isValid ones (order kept).  Returns the count, or -1 if
 // the id cannot be decoded.
+// Cell c (0 .. 2k - 1) of side `side` (0 bottom, 1 right, 2 top, 3 left) of that loop around the
+// cell of origin (x, y), edge e, resolution res; false where isValid drops it.
+MOSAIC_HD bool kloop_cell(int res, int32_t e, int32_t x, int32_t y, int k, int side, int c, int64_t* cell) {
+    // Int arithmetic, wrapping as the JVM's does (exact in int64 for |k| < 2^20, then
+    // truncated to 32 bits)
+    const int64_t X = x, Y = y, E = e, K = k, C = c;
+    int64_t qx, qy;
+    if (side == 0) {
+        qx = X + (C - K) * E;
+        qy = Y - K * E;
+    } else if (side == 1) {
+        qx = X + K * E;
+        qy = Y + (C - K) * E;
+    } else if (side == 2) {
+        qx = X + (K - C) * E;
+        qy = Y + K * E;
+    } else {
+        qx = X - K * E;
+        qy = Y + (K - C) * E;
+    }
+    const int32_t px = (int32_t)(uint32_t)(uint64_t)qx, py = (int32_t)(uint32_t)(uint64_t)qy;
+    *cell = 0;
+    point_to_index((double)px, (double)py, res, cell);
+    return is_valid(*cell);
+}
 MOSAIC_HD int kloop(int64_t id, int k, int64_t* out) {
     int res;
     int32_t e, x, y;
@@ -255,27 +280,8 @@ MOSAIC_HD int kloop(int64_t id, int k, int64_t* out) {
     int m = 0;
     for (int side = 0; side < 4; side++)
         for (int c = 0; c < 2 * k; c++) {
-            // Int arithmetic, wrapping as the JVM's does (exact in int64 for |k| < 2^20, then
-            // truncated to 32 bits)
-            const int64_t X = x, Y = y, E = e, K = k, C = c;
-            int64_t qx, qy;
-            if (side == 0) {
-                qx = X + (C - K) * E;
-                qy = Y - K * E;
-            } else if (side == 1) {
-                qx = X + K * E;
-                qy = Y + (C - K) * E;
-            } else if (side == 2) {
-                qx = X + (K - C) * E;
-                qy = Y + K * E;
-            } else {
-                qx = X - K * E;
-                qy = Y + (K - C) * E;
-            }
-            const int32_t px = (int32_t)(uint32_t)(uint64_t)qx, py = (int32_t)(uint32_t)(uint64_t)qy;
-            int64_t cell = 0;
-            point_to_index((double)px, (double)py, res, &cell);
-            if (is_valid(cell)) out[m++] = cell;
+            int64_t cell;
+            if (kloop_cell(res, e, x, y, k, side, c, &cell)) out[m++] = cell;
         }
     return m;
 }

@@ -2029,6 +2029,10 @@ struct Options {
     int64_t exact_cap = 0;
     // k_bin_cover's look-back poll limit (< 0: the uncompacted fallback at once, for its test)
     int bin_spin_cap = 1 << 20;
+    // geometry k-rings (geom_kring.hip): the search table's first size (a small value exercises its
+    // growth by rehashing) and the slot count past which a call returns MOSAIC_E_CAPACITY
+    int gk_table_log2 = 16;
+    int64_t gk_max_cells = (int64_t)1 << 27;
 };
 
 // Execution state of one calling thread on one context: its HIP stream (created on first use, or
@@ -2397,6 +2401,15 @@ int mosaic_ctx_exec(mosaic_ctx* ctx, int* device, void** stream, int* jdk, int* 
     return MOSAIC_OK;
 }
 
+// the "gk_table_log2" / "gk_max_cells" options, for geom_kring.hip
+int mosaic_ctx_gk_options(mosaic_ctx* ctx, int* table_log2, int64_t* max_cells) {
+    if (!ctx) return fail(MOSAIC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *table_log2 = ctx->opt.gk_table_log2;
+    *max_cells = ctx->opt.gk_max_cells;
+    return MOSAIC_OK;
+}
+
 int mosaic_abi_version(void) { return MOSAIC_ABI_VERSION; }
 const char* mosaic_last_error(void) { return g_last_error.c_str(); }
 
@@ -2685,6 +2698,12 @@ int mosaic_set_option(mosaic_ctx* ctx, const char* key, int64_t v) {
     } else if (k == "exact_cap") {
         if (v < 0) return fail(MOSAIC_E_ARG, "exact_cap must be >= 0");
         o.exact_cap = v;
+    } else if (k == "gk_table_log2") {
+        if (v < 4 || v > 30) return fail(MOSAIC_E_ARG, "gk_table_log2 must be in [4, 30]");
+        o.gk_table_log2 = (int)v;
+    } else if (k == "gk_max_cells") {
+        if (v < 16 || v > ((int64_t)1 << 31)) return fail(MOSAIC_E_ARG, "gk_max_cells must be in [16, 2^31]");
+        o.gk_max_cells = v;
     } else {
         return fail(MOSAIC_E_ARG, "unknown option " + k);
     }

@@ -40,6 +40,7 @@
 
 #include "../../include/mosaic_hip.h"
 #include "bng_device.h"
+#include "cell_lists.h"
 #include "h3_grid.h"
 #include "h3_polyfill.h"
 #include "pip_device.h"
@@ -48,12 +49,6 @@ using namespace mosaic;
 
 extern "C" int mosaic_tess_fail(int code, const char* msg);
 extern "C" int mosaic_ctx_exec(mosaic_ctx* ctx, int* device, void** stream, int* jdk, int* n_cu);
-
-struct mosaic_cell_lists {
-    std::vector<int64_t> offsets{0};
-    std::vector<int64_t> cells;
-    std::vector<int32_t> status;
-};
 
 namespace {
 
