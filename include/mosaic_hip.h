@@ -514,6 +514,37 @@ int mosaic_cell_lists_export_dist(const mosaic_cell_lists* lists, int32_t* dist)
  * thread's last mosaic_chips_kring (for mosaic_geometry_kring: without the tessellation), ms. */
 double mosaic_geometry_kring_last_ms(void);
 
+/* ---- st_distance over geometry columns (functions/MosaicContext.scala:146 ST_Distance ->
+ * expressions/geometry/ST_Distance.scala:34-36 -> JTS Geometry.distance; step 3 of the KNN iteration,
+ * models/knn/GridRingNeighbours.scala:153-156) ---- */
+/* A device-resident geometry column: immutable after creation, usable from any thread (like a chip
+ * table), freed with mosaic_geoms_destroy.  Rows are Point, MultiPoint, Polygon or MultiPolygon.
+ * _wkb: row i is wkb[offsets[i] .. offsets[i + 1]) (either byte order, ISO Z/M and EWKB variants);
+ *   valid[i] == 0 is a null row (MOSAIC_ROW_NULL); LineString, MultiLineString, GeometryCollection,
+ *   POINT EMPTY and undecodable rows are MOSAIC_ROW_PATH (the convention of
+ *   mosaic_point_geom_to_cell), not an error of the call.
+ * _arrays: polygonal geometries in the flat-ring layout of mosaic_polyfill (host pointers).
+ * _points: row i is POINT (x[i] y[i]); host or device pointers; a NaN coordinate is MOSAIC_ROW_PATH. */
+typedef struct mosaic_geoms mosaic_geoms;
+int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb,
+                            const uint8_t* valid /*nullable*/, mosaic_geoms** out);
+int mosaic_geoms_create_arrays(mosaic_ctx* ctx, int64_t n, const int64_t* geom_parts, const int64_t* part_rings,
+                               const int64_t* ring_offsets, const double* xy, mosaic_geoms** out);
+int mosaic_geoms_create_points(mosaic_ctx* ctx, const double* x, const double* y, int64_t n, mosaic_geoms** out);
+int mosaic_geoms_info(const mosaic_geoms* geoms, int64_t* n_geoms, int64_t* n_vertices, int64_t* n_row_path);
+int mosaic_geoms_destroy(mosaic_geoms* geoms);
+/* out[i] = st_distance(left[left_row[i]], right[right_row[i]]); left_row == right_row == NULL: row i
+ * with row i (n_pairs rows of both columns).  The value is that of the sequential definition in
+ * mosaic_amd/csrc/st_distance.h, bit for bit: 0.0 when either geometry is empty or one holds a
+ * component of the other, otherwise the smallest JTS segment / point distance over all facet pairs.
+ * status[i] (nullable): MOSAIC_ROW_OK; MOSAIC_ROW_NULL (either side null, out NaN); MOSAIC_ROW_PATH
+ * (either side a row-path row, out NaN).  A row index out of range: MOSAIC_E_ARG, nothing written.
+ * out / status / the row arrays: host or device pointers.  Options: "dist_tile" (segments per LDS
+ * tile, [1, 1024]), "dist_small_work" (facet pairs up to which one lane serves a pair) and
+ * "dist_prune" (0: no pruning, same result). */
+int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                       const int64_t* right_row, int64_t n_pairs, double* out, int32_t* status);
+
 /* getBufferRadius(geometry, res) per geometry (the radius mosaicFill buffers by, core/Mosaic.scala:68):
  * H3 (H3IndexSystem.scala:73-80): the largest distance (degrees) from the centroid of the cell
  * holding the geometry's JTS centroid (its indexToGeometry polygon's JTS centroid) to that polygon's

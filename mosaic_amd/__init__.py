@@ -4,7 +4,8 @@ Product path: libmosaic_hip.so (mosaic_amd/csrc, HIP for gfx950) behind the C AB
 include/mosaic_hip.h; this package is the host-side mirror of the reference's function surface.
 """
 from ._native import IllegalStateException, MosaicError, NativeUnavailable  # noqa: F401
-from .context import BNGIndexSystem, ChipTable, H3IndexSystem, MosaicContext, RowPathRequired  # noqa: F401
+from .context import (BNGIndexSystem, ChipTable, GeometryTable, H3IndexSystem, MosaicContext,  # noqa: F401
+                      RowPathRequired)
 
-__all__ = ["MosaicContext", "ChipTable", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
+__all__ = ["MosaicContext", "ChipTable", "GeometryTable", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
            "MosaicError", "NativeUnavailable"]

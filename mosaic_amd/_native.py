@@ -44,7 +44,8 @@ EXPORTS = [
     "mosaic_intersection_aggregate", "mosaic_thread_release", "mosaic_thread_count", "mosaic_stream_wait_event",
     "mosaic_intersection_aggregate_geometry", "mosaic_isect_geoms_info", "mosaic_isect_geoms_export",
     "mosaic_isect_geoms_destroy", "mosaic_chips_kring", "mosaic_geometry_kring", "mosaic_cell_lists_export_dist",
-    "mosaic_geometry_kring_last_ms",
+    "mosaic_geometry_kring_last_ms", "mosaic_geoms_create_wkb", "mosaic_geoms_create_arrays",
+    "mosaic_geoms_create_points", "mosaic_geoms_info", "mosaic_geoms_destroy", "mosaic_st_distance",
 ]
 
 GEOM_WKB = 0
@@ -154,6 +155,12 @@ def lib():
         "mosaic_geometry_kring": ([vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, ctypes.POINTER(vp)], i32),
         "mosaic_cell_lists_export_dist": ([vp, vp], i32),
         "mosaic_geometry_kring_last_ms": ([], ctypes.c_double),
+        "mosaic_geoms_create_wkb": ([vp, i64, vp, vp, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_geoms_create_arrays": ([vp, i64, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_geoms_create_points": ([vp, vp, vp, i64, ctypes.POINTER(vp)], i32),
+        "mosaic_geoms_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "mosaic_geoms_destroy": ([vp], i32),
+        "mosaic_st_distance": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
         "mosaic_buffer_radius": ([vp, i32, i32, i64, vp, vp, vp, vp, vp], i32),
         "mosaic_chip_table_create_arrays": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_intersection_aggregate": ([vp, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),

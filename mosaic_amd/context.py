@@ -325,6 +325,86 @@ class ChipTable:
             pass
 
 
+_WKB_ROW_PATH = b"\x00\x00\x00\x00\x02\x00\x00\x00\x00"  # LINESTRING EMPTY: stands for a row the engine does not serve
+
+
+def _wkt_row_wkb(text):
+    """A WKT row as the WKB the geometry column decodes; what wkb.read_wkt does not read (line
+    geometries, collections, malformed text) becomes a row for the row path."""
+    head = text.split("(", 1)[0].split()
+    if not head or head[0].upper() not in ("POINT", "MULTIPOINT", "POLYGON", "MULTIPOLYGON"):
+        return _WKB_ROW_PATH
+    try:
+        kind, g = W.read_wkt(text)
+    except (ValueError, IndexError):
+        return _WKB_ROW_PATH
+    if kind == "point":
+        return W.point_wkb(*(g if g is not None else (float("nan"), float("nan"))))
+    if kind == "multipoint":
+        return W.multipoint_wkb(g)
+    return W.geometry_wkb(g) if len(g) != 1 else W.polygon_wkb(g[0])
+
+
+class GeometryTable:
+    """A device-resident geometry column (mosaic_geoms): Point, MultiPoint, Polygon and MultiPolygon
+    rows in the flat ring layout, immutable after creation and usable from any thread, for
+    ``MosaicContext.st_distance``.  The KNN iteration evaluates distances against the same candidate
+    column on every round (models/knn/GridRingNeighbours.scala:76-99), so the column outlives a call.
+    Built by ``MosaicContext.geometry_table``; ``close()`` frees the device memory."""
+
+    def __init__(self, ctx, geoms):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        lib = N.lib()
+        rows_given = isinstance(geoms, (list, tuple)) and any(g is None or isinstance(g, (str, bytes, bytearray, memoryview))
+                                                            for g in geoms)
+        xy = None if hasattr(geoms, "geom_parts") or rows_given else _points_xy(geoms)
+        if hasattr(geoms, "geom_parts"):  # a PolygonSet
+            N.check(lib.mosaic_geoms_create_arrays(ctx.handle, len(geoms), N.ptr(geoms.geom_parts), N.ptr(geoms.part_rings),
+                                                   N.ptr(geoms.ring_offsets), N.ptr(geoms.xy), ctypes.byref(h)))
+        elif xy is not None:
+            x, y = xy
+            if len(x) != len(y):
+                raise ValueError("x and y have different lengths")
+            ctx._order(x, y)
+            N.check(lib.mosaic_geoms_create_points(ctx.handle, N.ptr(x), N.ptr(y), len(x), ctypes.byref(h)))
+        else:
+            if isinstance(geoms, (str, bytes, bytearray)):
+                geoms = [geoms]
+            rows = [_wkt_row_wkb(g) if isinstance(g, str) else g for g in geoms]
+            _, offsets, data, valid = geometry_column(rows)
+            N.check(lib.mosaic_geoms_create_wkb(ctx.handle, len(rows), N.ptr(offsets), N.ptr(data), N.ptr(valid),
+                                                ctypes.byref(h)))
+        self.handle = h
+        info = self.info()
+        self.n_geoms = info["n_geoms"]
+
+    def __len__(self):
+        return self.n_geoms
+
+    def info(self):
+        n, v, p = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        N.check(N.lib().mosaic_geoms_info(self.handle, ctypes.byref(n), ctypes.byref(v), ctypes.byref(p)))
+        return dict(n_geoms=n.value, n_vertices=v.value, n_row_path=p.value)
+
+    def close(self):
+        if self.handle:
+            N.lib().mosaic_geoms_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MosaicContext:
     """``MosaicContext.build(indexSystem, geometryAPI)``; geometry API is JTS semantics only."""
 
@@ -627,6 +707,80 @@ class MosaicContext:
                                            N.ptr(out)))
         return out.astype(bool)
 
+    # ---- st_distance ----
+    def geometry_table(self, geoms):
+        """A ``GeometryTable``: ``geoms`` as a device-resident geometry column.  Accepts a PolygonSet;
+        a sequence of WKB (bytes) or WKT (str) rows of POINT / MULTIPOINT / POLYGON / MULTIPOLYGON,
+        None = null (one row may be given bare); or points as an ``(x, y)`` pair or an ``[n, 2]``
+        array or tensor, on the host or the device.  Line geometries, collections, POINT EMPTY and
+        undecodable rows are kept as rows for the reference's row path."""
+        return GeometryTable(self, geoms)
+
+    def st_distance(self, left, right, pairs=None, return_status=False):
+        """st_distance(left, right) (functions/MosaicContext.scala:146 ST_Distance ->
+        expressions/geometry/ST_Distance.scala:34-36 -> core/geometry/MosaicGeometryJTS.distance ->
+        JTS 1.19 Geometry.distance / DistanceOp.distance; docs/source/api/spatial-functions.rst:416-471),
+        and step 3 of the KNN iteration (models/knn/GridRingNeighbours.scala:153-156), on this
+        context's GPU (mosaic_st_distance): 0.0 when either geometry is empty or one contains a
+        component of the other, otherwise the smallest JTS segment / point distance over all pairs of
+        facets -- the bits of the sequential definition in mosaic_amd/csrc/st_distance.h.
+
+        ``left`` / ``right``: ``GeometryTable``s, or anything ``geometry_table`` accepts (the table
+        is then built and closed inside the call).  ``pairs=None`` is row-wise: the lengths match, or
+        one side is a single geometry that every row of the other is measured against (as in
+        ``st_contains``).  ``pairs=(left_idx, right_idx)`` evaluates exactly those (left row, right
+        row) pairs; the index arrays may live on the device.  Returns a float64 array with NaN on
+        null rows.  Rows either side leaves to the row path raise ``RowPathRequired`` with the pair
+        indices, unless return_status, which adds the pairs' status array (ROW_OK / ROW_NULL /
+        ROW_PATH; NaN on the row-path pairs too)."""
+        own = []
+        try:
+            tabs = []
+            for side in (left, right):
+                if not isinstance(side, GeometryTable):
+                    side = self.geometry_table(side)
+                    own.append(side)
+                tabs.append(side)
+            lt, rt = tabs
+            if pairs is None:
+                nl, nr = len(lt), len(rt)
+                if nl == nr:
+                    n, li, ri = nl, None, None
+                elif nl == 1 or nr == 1:
+                    n = max(nl, nr)
+                    li = np.zeros(n, np.int64) if nl == 1 else np.arange(n, dtype=np.int64)
+                    ri = np.zeros(n, np.int64) if nr == 1 else np.arange(n, dtype=np.int64)
+                else:
+                    raise ValueError(f"row-wise st_distance of {nl} and {nr} rows: the lengths must match "
+                                     "(or one side is a single geometry)")
+            else:
+                li, ri = pairs
+                if _is_torch(li) or _is_torch(ri):
+                    import torch
+
+                    li = li.to(torch.int64).contiguous()
+                    ri = ri.to(torch.int64).contiguous()
+                    self._order(li, ri)
+                else:
+                    li = np.ascontiguousarray(li, np.int64)
+                    ri = np.ascontiguousarray(ri, np.int64)
+                if len(li) != len(ri):
+                    raise ValueError("pairs: the two index arrays have different lengths")
+                n = len(li)
+            out = np.zeros(n, np.float64)
+            status = np.zeros(n, np.int32)
+            N.check(N.lib().mosaic_st_distance(self.handle, lt.handle, rt.handle, N.ptr(li), N.ptr(ri), n, N.ptr(out),
+                                               N.ptr(status)))
+        finally:
+            for t in own:
+                t.close()
+        if return_status:
+            return out, status
+        path = np.flatnonzero(status == N.ROW_PATH)
+        if len(path):
+            raise RowPathRequired(path)
+        return out
+
     # ---- the chip join ----
     def grid_tessellateexplode(self, polygons, resolution, keep_core_geom=True, densify=1):
         """grid_tessellateexplode(geom, res, keepCoreGeom) (MosaicContext.scala functions ->
@@ -654,7 +808,6 @@ class MosaicContext:
         """Quickstart join + filter + groupBy(polygon).count(): int64 count per polygon key.
         ``out`` (optional, >= n_polygons int64, host or device) receives the counts."""
         x, y = _f64(x), _f64(y)
-        self._order(x, y, out)
         n = int(x.shape[0])
         if out is not None:
             counts = out
@@ -664,6 +817,9 @@ class MosaicContext:
             counts = torch.zeros(max(chips.n_polygons, 1), dtype=torch.int64, device=x.device)
         else:
             counts = np.zeros(max(chips.n_polygons, 1), np.int64)
+        # after the allocation: torch fills `counts` on its own stream, and that fill has to be ordered
+        # before the join like the inputs (a late fill would clear what the join counted)
+        self._order(x, y, counts)
         N.check(N.lib().mosaic_pip_join_count(self.handle, chips.handle, N.ptr(x), N.ptr(y), n, N.ptr(counts)))
         return counts[:chips.n_polygons]
 

@@ -47,6 +47,7 @@
 #include "point_decode.h"
 #include "raster.h"
 #include "raster_build.h"
+#include "st_distance.h"
 #include "tess_clip.h"
 #include "tess_gpu.h"
 #include "tiles.h"
@@ -86,6 +87,7 @@ int kring_slow_host(uint64_t origin, int k, int loop, int64_t* out, int64_t* tab
 extern "C" uint64_t mosaic_layout_join_binned(void);
 extern "C" uint64_t mosaic_layout_join_stream(void);
 extern "C" uint64_t mosaic_layout_tess_clip(void);
+extern "C" uint64_t mosaic_layout_st_distance(void);
 
 template <int GRID, bool LDS_COUNTS, bool PAIRS>
 __global__ void __launch_bounds__(256) k_join_raster(JoinArgs a) {
@@ -2033,6 +2035,12 @@ struct Options {
     // growth by rehashing) and the slot count past which a call returns MOSAIC_E_CAPACITY
     int gk_table_log2 = 16;
     int64_t gk_max_cells = (int64_t)1 << 27;
+    // st_distance (st_distance.hip): segments of the staged side per LDS tile of k_dist_block, the
+    // facet-pair count up to which a pair goes to k_dist_small, and pruning by box bounds (0: off,
+    // for measurements; the result is the same)
+    int dist_tile = 16;
+    int64_t dist_small_work = 512;
+    int dist_prune = 1;
 };
 
 // Execution state of one calling thread on one context: its HIP stream (created on first use, or
@@ -2410,6 +2418,16 @@ int mosaic_ctx_gk_options(mosaic_ctx* ctx, int* table_log2, int64_t* max_cells) 
     return MOSAIC_OK;
 }
 
+// the "dist_tile" / "dist_small_work" / "dist_prune" options, for st_distance.hip
+int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune) {
+    if (!ctx) return fail(MOSAIC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *tile = ctx->opt.dist_tile;
+    *small_work = ctx->opt.dist_small_work;
+    *prune = ctx->opt.dist_prune;
+    return MOSAIC_OK;
+}
+
 int mosaic_abi_version(void) { return MOSAIC_ABI_VERSION; }
 const char* mosaic_last_error(void) { return g_last_error.c_str(); }
 
@@ -2512,7 +2530,8 @@ int mosaic_init(int device, mosaic_ctx** out) {
     // objects compiled against different revisions of the shared headers (a hand-linked A/B library)
     // would pass structs with shifted fields between translation units: refuse to run
     if (mosaic_layout_join_binned() != mosaic_layout_fingerprint() || mosaic_layout_join_stream() != mosaic_layout_fingerprint() ||
-        mosaic_layout_tess_clip() != mosaic::tessll::layout_fingerprint())
+        mosaic_layout_tess_clip() != mosaic::tessll::layout_fingerprint() ||
+        mosaic_layout_st_distance() != mosaic::dist::layout_fingerprint())
         return fail(MOSAIC_E_ARG, "libmosaic_hip.so links objects built against different struct layouts (rebuild every object)");
     thp_off_once();
     int count = 0;
@@ -2704,6 +2723,14 @@ int mosaic_set_option(mosaic_ctx* ctx, const char* key, int64_t v) {
     } else if (k == "gk_max_cells") {
         if (v < 16 || v > ((int64_t)1 << 31)) return fail(MOSAIC_E_ARG, "gk_max_cells must be in [16, 2^31]");
         o.gk_max_cells = v;
+    } else if (k == "dist_tile") {
+        if (v < 1 || v > 1024) return fail(MOSAIC_E_ARG, "dist_tile must be in [1, 1024]");
+        o.dist_tile = (int)v;
+    } else if (k == "dist_small_work") {
+        if (v < 0) return fail(MOSAIC_E_ARG, "dist_small_work must be >= 0");
+        o.dist_small_work = v;
+    } else if (k == "dist_prune") {
+        o.dist_prune = v != 0;
     } else {
         return fail(MOSAIC_E_ARG, "unknown option " + k);
     }

@@ -1,0 +1,559 @@
+// st_distance over device-resident geometry columns (mosaic_geoms_*, mosaic_st_distance): JTS
+// Geometry.distance for Point / MultiPoint / Polygon / MultiPolygon rows, on (left row, right row)
+// pairs -- step 3 of the reference's KNN iteration (models/knn/GridRingNeighbours.scala:153-156) and
+// the public ST_Distance (expressions/geometry/ST_Distance.scala:34-36).  st_distance.h holds the
+// semantics, the arithmetic and the sequential driver whose bits these kernels return.
+//
+// A column is the GeomStore layout of pip_device.h in HBM plus a kind per part (point / polygon), a
+// facet count per geometry and a status per row; it is immutable after creation.
+//
+// Per call:
+//   k_dist_plan    one lane per pair: row range check, row status, work = facets(left) x facets(right);
+//                  pair ids with work <= dist_small_work are appended to the front of one list, the
+//                  others to its back (one atomicAdd per wave and list)
+//   k_dist_fill    status[] of every pair, NaN for the null / row-path ones (only after the host has
+//                  seen that no row index was out of range: such a call writes nothing)
+//   k_dist_small   one lane per pair: the sequential driver dist::distance
+//   k_dist_block   one workgroup per pair.  Containment first, one lane per (polygon part, component)
+//                  and direction.  Then the side with fewer facets is staged in LDS, a tile of
+//                  dist_tile segments at a time, and the other side's segments are streamed across the
+//                  lanes, each lane keeping a running minimum.  The workgroup's current minimum lives
+//                  in LDS as the bit pattern of a non-negative double (integer atomicMin); a
+//                  (tile, streamed geometry), (tile, streamed ring) or (tile, streamed segment) block is
+//                  skipped only when dist::box_lower_bound of it is strictly greater than that minimum,
+//                  and a minimum of 0 ends the pair.  The lanes' minima are reduced within each wave by
+//                  shuffles, then across the waves through LDS.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/mosaic_hip.h"
+#include "geoms_build.h"
+#include "st_distance.h"
+
+using namespace mosaic;
+
+extern "C" int mosaic_tess_fail(int code, const char* msg);
+extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune);
+
+struct mosaic_geoms {
+    int device = 0;
+    int64_t n_geoms = 0, n_vertices = 0, n_row_path = 0;
+    pip::Vec2* verts = nullptr;
+    uint32_t* ring_start = nullptr;
+    pip::Box* ring_bbox = nullptr;
+    uint32_t* part_ring = nullptr;
+    uint8_t* part_kind = nullptr;
+    uint32_t* geom_part = nullptr;
+    pip::Box* geom_bbox = nullptr;
+    uint32_t* geom_facets = nullptr;
+    int32_t* row_status = nullptr;
+    ~mosaic_geoms() {
+        for (void* p : {(void*)verts, (void*)ring_start, (void*)ring_bbox, (void*)part_ring, (void*)part_kind,
+                        (void*)geom_part, (void*)geom_bbox, (void*)geom_facets, (void*)row_status})
+            if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxTile = 1024;
+
+#define SD_RC(expr)          \
+    do {                     \
+        int _rc = (expr);    \
+        if (_rc) return _rc; \
+    } while (0)
+#define SD_HIP(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess)                                                                                 \
+            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                \
+                                    (std::string("st_distance: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
+    } while (0)
+
+struct Col {
+    pip::GeomStore s;
+    const uint8_t* part_kind;
+    const uint32_t* facets;
+    const int32_t* status;
+    int64_t n;
+};
+
+Col view(const mosaic_geoms* g) {
+    return Col{pip::GeomStore{g->verts, g->ring_start, g->ring_bbox, g->part_ring, g->geom_part, g->geom_bbox},
+               g->part_kind, g->geom_facets, g->row_status, g->n_geoms};
+}
+
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+};
+
+bool is_device_ptr(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+__device__ inline unsigned long long wave_append(unsigned long long* counter, bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if (m == 0) return 0;
+    const int leader = __ffsll((long long)m) - 1;
+    const int lane = (int)__lane_id();
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+    base = (unsigned long long)__shfl((long long)base, leader, 64);
+    return base + (unsigned long long)__popcll(m & (((unsigned long long)1 << lane) - 1));
+}
+
+// a point column built on the device: row i is the point part (x[i], y[i]); a NaN coordinate is POINT EMPTY
+__global__ void __launch_bounds__(kBlock) k_points_col(const double* x, const double* y, int64_t n, pip::Vec2* verts,
+                                                       uint32_t* ring_start, pip::Box* ring_bbox, uint32_t* part_ring,
+                                                       uint8_t* part_kind, uint32_t* geom_part, pip::Box* geom_bbox,
+                                                       uint32_t* facets, int32_t* status, unsigned long long* n_path) {
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 <= n; i0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = i0 + threadIdx.x;
+        bool path = false;
+        if (i <= n) {
+            ring_start[i] = (uint32_t)i;
+            part_ring[i] = (uint32_t)i;
+            geom_part[i] = (uint32_t)i;
+        }
+        if (i < n) {
+            const double px = x[i], py = y[i];
+            path = px != px || py != py;
+            verts[i] = pip::Vec2{px, py};
+            ring_bbox[i] = pip::Box{px, py, px, py};
+            geom_bbox[i] = pip::Box{px, py, px, py};
+            part_kind[i] = kPartPoint;
+            facets[i] = 1;
+            status[i] = path ? MOSAIC_ROW_PATH : MOSAIC_ROW_OK;
+        }
+        const unsigned long long m = __ballot(path);
+        if (m && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(n_path, (unsigned long long)__popcll(m));
+    }
+}
+
+struct PlanArgs {
+    Col L, R;
+    const int64_t *lrow, *rrow;  // both null: pair i is (row i, row i)
+    int64_t n;
+    unsigned long long small_work;
+    int32_t* plan;                 // the pair's status
+    int64_t* list;                 // small pairs from the front, block pairs from the back
+    unsigned long long* counts;    // [0] small, [1] block, [2] row indices out of range
+};
+
+__global__ void __launch_bounds__(kBlock) k_dist_plan(PlanArgs a) {
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < a.n; i0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = i0 + threadIdx.x;
+        bool small = false, block = false;
+        if (i < a.n) {
+            const int64_t g = a.lrow ? a.lrow[i] : i, h = a.rrow ? a.rrow[i] : i;
+            if (g < 0 || g >= a.L.n || h < 0 || h >= a.R.n) {
+                atomicAdd(&a.counts[2], 1ull);
+                a.plan[i] = -1;
+            } else {
+                const int32_t sl = a.L.status[g], sr = a.R.status[h];
+                int32_t st = MOSAIC_ROW_OK;
+                if (sl == MOSAIC_ROW_NULL || sr == MOSAIC_ROW_NULL)
+                    st = MOSAIC_ROW_NULL;
+                else if (sl != MOSAIC_ROW_OK || sr != MOSAIC_ROW_OK)
+                    st = MOSAIC_ROW_PATH;
+                a.plan[i] = st;
+                if (st == MOSAIC_ROW_OK) {
+                    const unsigned long long work = (unsigned long long)a.L.facets[g] * a.R.facets[h];
+                    small = work <= a.small_work;
+                    block = !small;
+                }
+            }
+        }
+        const unsigned long long ps = wave_append(&a.counts[0], small);
+        const unsigned long long pb = wave_append(&a.counts[1], block);
+        if (small) a.list[ps] = i;
+        if (block) a.list[a.n - 1 - (int64_t)pb] = i;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_dist_fill(const int32_t* plan, int64_t n, double* out, int32_t* status) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t st = plan[i];
+        if (status) status[i] = st;
+        if (st != MOSAIC_ROW_OK) out[i] = __longlong_as_double(0x7ff8000000000000LL);
+    }
+}
+
+struct DistArgs {
+    Col L, R;
+    const int64_t *lrow, *rrow;
+    const int64_t* list;
+    int64_t n_list;
+    double* out;
+    int tile;
+    int prune;
+};
+
+__global__ void __launch_bounds__(kBlock) k_dist_small(DistArgs a) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n_list; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = a.list[k];
+        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        a.out[i] = dist::distance(a.L.s, g, a.R.s, h);
+    }
+}
+
+__device__ inline double lds_min(const unsigned long long* p) {
+    return __longlong_as_double((long long)*(const volatile unsigned long long*)p);
+}
+
+__global__ void __launch_bounds__(kBlock) k_dist_block(DistArgs a) {
+    __shared__ pip::Vec2 s_v[kMaxTile + 1];
+    __shared__ pip::Box s_box;
+    __shared__ unsigned long long s_min, s_snap;
+    __shared__ int s_hit;
+    __shared__ double s_wave[kBlock / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t T = (uint32_t)a.tile;
+    for (int64_t k = blockIdx.x; k < a.n_list; k += gridDim.x) {
+        const int64_t i = a.list[k];
+        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        // S: the staged side (fewer facets), W: the streamed side; flip: S is the right geometry
+        const bool flip = a.L.facets[g] > a.R.facets[h];
+        const Col& CS = flip ? a.R : a.L;
+        const Col& CW = flip ? a.L : a.R;
+        const pip::GeomStore& S = CS.s;
+        const pip::GeomStore& W = CW.s;
+        const uint32_t gs = flip ? h : g, gw = flip ? g : h;
+        __syncthreads();  // the previous pair's readers of s_hit / s_wave are done
+        if (tid == 0) {
+            s_hit = 0;
+            s_min = (unsigned long long)__double_as_longlong(INFINITY);
+        }
+        __syncthreads();
+        // ---- containment: (polygon part p of one side, component q of the other), both directions ----
+        {
+            const uint32_t ps0 = S.geom_part[gs], nps = S.geom_part[gs + 1] - ps0;
+            const uint32_t pw0 = W.geom_part[gw], npw = W.geom_part[gw + 1] - pw0;
+            const uint64_t tasks = 2ull * nps * npw;
+            for (uint64_t t = tid; t < tasks; t += kBlock) {
+                if (*(volatile int*)&s_hit) break;
+                const uint64_t u = t >> 1;
+                const uint32_t p = ps0 + (uint32_t)(u / npw), q = pw0 + (uint32_t)(u % npw);
+                bool hit;
+                if (t & 1)
+                    hit = CW.part_kind[q] == kPartPolygon && dist::component_in_part(W, q, S, p);
+                else
+                    hit = CS.part_kind[p] == kPartPolygon && dist::component_in_part(S, p, W, q);
+                if (hit) s_hit = 1;
+            }
+        }
+        __syncthreads();
+        if (s_hit) {  // uniform
+            if (tid == 0) a.out[i] = 0.0;
+            continue;
+        }
+        // ---- facets ----
+        uint32_t rs0, rs1, rw0, rw1;
+        dist::geom_rings(S, gs, rs0, rs1);
+        dist::geom_rings(W, gw, rw0, rw1);
+        const pip::Box wbox = W.geom_bbox[gw];
+        double m = INFINITY;
+        bool done = false;
+        for (uint32_t rs = rs0; rs < rs1 && !done; rs++) {
+            const uint32_t v0 = S.ring_start[rs], n = S.ring_start[rs + 1] - v0;
+            const uint32_t nf = dist::ring_facets(n);
+            for (uint32_t f0 = 0; f0 < nf; f0 += T) {
+                const uint32_t cnt = nf - f0 < T ? nf - f0 : T;
+                __syncthreads();  // the previous tile's readers of s_v / s_box are done
+                for (uint32_t t = tid; t <= cnt; t += kBlock) {
+                    const uint32_t vi = f0 + t < n ? f0 + t : n - 1;
+                    s_v[t] = S.verts[v0 + vi];
+                }
+                if (tid == 0) s_snap = s_min;
+                __syncthreads();
+                if (s_snap == 0) {  // uniform: a zero ends the pair
+                    done = true;
+                    break;
+                }
+                if (tid < 64) {
+                    pip::Box b = {INFINITY, INFINITY, -INFINITY, -INFINITY};
+                    for (uint32_t t = tid; t <= cnt; t += 64) {
+                        const pip::Vec2 v = s_v[t];
+                        b.minx = fmin(b.minx, v.x);
+                        b.miny = fmin(b.miny, v.y);
+                        b.maxx = fmax(b.maxx, v.x);
+                        b.maxy = fmax(b.maxy, v.y);
+                    }
+                    for (int off = 32; off; off >>= 1) {
+                        b.minx = fmin(b.minx, __shfl_xor(b.minx, off, 64));
+                        b.miny = fmin(b.miny, __shfl_xor(b.miny, off, 64));
+                        b.maxx = fmax(b.maxx, __shfl_xor(b.maxx, off, 64));
+                        b.maxy = fmax(b.maxy, __shfl_xor(b.maxy, off, 64));
+                    }
+                    if (tid == 0) s_box = b;
+                }
+                __syncthreads();
+                const pip::Box tb = s_box;
+                if (a.prune && dist::box_lower_bound(tb, wbox) > __longlong_as_double((long long)s_snap)) continue;  // uniform
+                for (uint32_t rw = rw0; rw < rw1; rw++) {
+                    const uint32_t w0 = W.ring_start[rw], nw = W.ring_start[rw + 1] - w0;
+                    const uint32_t nfw = dist::ring_facets(nw);
+                    if (a.prune && dist::box_lower_bound(tb, W.ring_bbox[rw]) > lds_min(&s_min)) continue;
+                    for (uint32_t j = tid; j < nfw; j += kBlock) {
+                        pip::Vec2 C, D;
+                        dist::ring_facet(W.verts + w0, nw, j, C, D);
+                        const double cur = lds_min(&s_min);
+                        if (cur == 0) break;
+                        if (a.prune) {
+                            const pip::Box sb = {C.x < D.x ? C.x : D.x, C.y < D.y ? C.y : D.y, C.x > D.x ? C.x : D.x,
+                                                 C.y > D.y ? C.y : D.y};
+                            if (dist::box_lower_bound(tb, sb) > cur) continue;
+                        }
+                        double mm = m;
+                        if (flip) {
+                            for (uint32_t t = 0; t < cnt; t++) mm = dist::min2(mm, dist::segment_segment(C, D, s_v[t], s_v[t + 1]));
+                        } else {
+                            for (uint32_t t = 0; t < cnt; t++) mm = dist::min2(mm, dist::segment_segment(s_v[t], s_v[t + 1], C, D));
+                        }
+                        if (mm < m) {
+                            m = mm;
+                            atomicMin(&s_min, (unsigned long long)__double_as_longlong(m));
+                        }
+                    }
+                }
+            }
+        }
+        // ---- the lanes' minima: within the wave by shuffles, across the waves through LDS ----
+        for (int off = 32; off; off >>= 1) m = dist::min2(m, __shfl_xor(m, off, 64));
+        if ((tid & 63) == 0) s_wave[tid >> 6] = m;
+        __syncthreads();
+        if (tid == 0) {
+            double r = s_wave[0];
+            for (int w = 1; w < kBlock / 64; w++) r = dist::min2(r, s_wave[w]);
+            a.out[i] = r;
+        }
+    }
+}
+
+template <class T>
+int upload(T** dst, const std::vector<T>& src) {
+    SD_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
+    if (!src.empty()) SD_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return MOSAIC_OK;
+}
+
+int upload_column(int device, const GeomColumn& c, mosaic_geoms** out) {
+    if (c.too_large()) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry column: 2^32 - 1 vertices or rows at the most");
+    std::unique_ptr<mosaic_geoms> g(new mosaic_geoms());
+    g->device = device;
+    g->n_geoms = c.size();
+    g->n_vertices = (int64_t)c.b.verts.size();
+    g->n_row_path = c.n_row_path;
+    SD_RC(upload(&g->verts, c.b.verts));
+    SD_RC(upload(&g->ring_start, c.b.ring_start));
+    SD_RC(upload(&g->ring_bbox, c.b.ring_bbox));
+    SD_RC(upload(&g->part_ring, c.b.part_ring));
+    SD_RC(upload(&g->part_kind, c.part_kind));
+    SD_RC(upload(&g->geom_part, c.b.geom_part));
+    SD_RC(upload(&g->geom_bbox, c.b.geom_bbox));
+    SD_RC(upload(&g->geom_facets, c.geom_facets));
+    SD_RC(upload(&g->row_status, c.row_status));
+    *out = g.release();
+    return MOSAIC_OK;
+}
+
+// src (n elements, host or device) as a device pointer; a host array is copied into `stage`
+template <class T>
+int on_device(const T* src, int64_t n, DevMem& stage, hipStream_t stream, const T** out) {
+    if (is_device_ptr(src)) {
+        *out = src;
+        return MOSAIC_OK;
+    }
+    SD_HIP(stage.alloc((size_t)n * sizeof(T)));
+    SD_HIP(hipMemcpyAsync(stage.p, src, (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
+    *out = (const T*)stage.p;
+    return MOSAIC_OK;
+}
+
+int64_t blocks_for(int64_t n, int64_t cap) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mosaic_layout_st_distance(void) { return dist::layout_fingerprint(); }
+
+int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb, const uint8_t* valid,
+                            mosaic_geoms** out) {
+    if (!ctx || !out || n < 0 || (n > 0 && (!offsets || !wkb))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    *out = nullptr;
+    int device = 0, jdk = 8, n_cu = 256;
+    void* stream = nullptr;
+    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    GeomColumn c;
+    for (int64_t i = 0; i < n; i++) {
+        if (offsets[i + 1] < offsets[i]) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: offsets decrease");
+        if (valid && !valid[i])
+            c.add_empty(kRowNull);
+        else
+            c.add_wkb(wkb + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    }
+    return upload_column(device, c, out);
+}
+
+int mosaic_geoms_create_arrays(mosaic_ctx* ctx, int64_t n, const int64_t* geom_parts, const int64_t* part_rings,
+                               const int64_t* ring_offsets, const double* xy, mosaic_geoms** out) {
+    if (!ctx || !out || n < 0 || !geom_parts || (n > 0 && (!part_rings || !ring_offsets)))
+        return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    *out = nullptr;
+    int device = 0, jdk = 8, n_cu = 256;
+    void* stream = nullptr;
+    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    GeomColumn c;
+    if (geom_parts[0] != 0 || !c.add_arrays(n, geom_parts, part_rings, ring_offsets, xy))
+        return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
+    return upload_column(device, c, out);
+}
+
+int mosaic_geoms_create_points(mosaic_ctx* ctx, const double* x, const double* y, int64_t n, mosaic_geoms** out) {
+    if (!ctx || !out || n < 0 || (n > 0 && (!x || !y))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    *out = nullptr;
+    if (n >= 0xffffffffLL) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry column: 2^32 - 1 vertices or rows at the most");
+    int device = 0, jdk = 8, n_cu = 256;
+    void* stream_v = nullptr;
+    SD_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
+    hipStream_t stream = (hipStream_t)stream_v;
+    std::unique_ptr<mosaic_geoms> g(new mosaic_geoms());
+    g->device = device;
+    g->n_geoms = n;
+    g->n_vertices = n;
+    const size_t n1 = (size_t)n + 1;
+    SD_HIP(hipMalloc((void**)&g->verts, n1 * sizeof(pip::Vec2)));
+    SD_HIP(hipMalloc((void**)&g->ring_start, n1 * sizeof(uint32_t)));
+    SD_HIP(hipMalloc((void**)&g->ring_bbox, n1 * sizeof(pip::Box)));
+    SD_HIP(hipMalloc((void**)&g->part_ring, n1 * sizeof(uint32_t)));
+    SD_HIP(hipMalloc((void**)&g->part_kind, n1));
+    SD_HIP(hipMalloc((void**)&g->geom_part, n1 * sizeof(uint32_t)));
+    SD_HIP(hipMalloc((void**)&g->geom_bbox, n1 * sizeof(pip::Box)));
+    SD_HIP(hipMalloc((void**)&g->geom_facets, n1 * sizeof(uint32_t)));
+    SD_HIP(hipMalloc((void**)&g->row_status, n1 * sizeof(int32_t)));
+    DevMem sx, sy, cnt;
+    const double *dx = nullptr, *dy = nullptr;
+    if (n > 0) {
+        SD_RC(on_device(x, n, sx, stream, &dx));
+        SD_RC(on_device(y, n, sy, stream, &dy));
+    }
+    SD_HIP(cnt.alloc(sizeof(unsigned long long)));
+    SD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_points_col, dim3((unsigned)blocks_for(n + 1, (int64_t)n_cu * 16)), dim3(kBlock), 0, stream, dx, dy, n,
+                       g->verts, g->ring_start, g->ring_bbox, g->part_ring, g->part_kind, g->geom_part, g->geom_bbox,
+                       g->geom_facets, g->row_status, (unsigned long long*)cnt.p);
+    SD_HIP(hipGetLastError());
+    unsigned long long n_path = 0;
+    SD_HIP(hipMemcpyAsync(&n_path, cnt.p, sizeof(n_path), hipMemcpyDeviceToHost, stream));
+    SD_HIP(hipStreamSynchronize(stream));
+    g->n_row_path = (int64_t)n_path;
+    *out = g.release();
+    return MOSAIC_OK;
+}
+
+int mosaic_geoms_info(const mosaic_geoms* g, int64_t* n_geoms, int64_t* n_vertices, int64_t* n_row_path) {
+    if (!g) return mosaic_tess_fail(MOSAIC_E_ARG, "null geometry column");
+    if (n_geoms) *n_geoms = g->n_geoms;
+    if (n_vertices) *n_vertices = g->n_vertices;
+    if (n_row_path) *n_row_path = g->n_row_path;
+    return MOSAIC_OK;
+}
+
+int mosaic_geoms_destroy(mosaic_geoms* g) {
+    if (!g) return MOSAIC_OK;
+    (void)hipSetDevice(g->device);
+    delete g;
+    return MOSAIC_OK;
+}
+
+int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                       const int64_t* right_row, int64_t n_pairs, double* out, int32_t* status) {
+    if (!ctx || !left || !right || n_pairs < 0 || (n_pairs > 0 && !out))
+        return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    if ((left_row == nullptr) != (right_row == nullptr))
+        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: left_row and right_row are both given or both null");
+    if (!left_row && (n_pairs > left->n_geoms || n_pairs > right->n_geoms))
+        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: row-wise form with more pairs than rows");
+    int device = 0, jdk = 8, n_cu = 256, tile = 16, prune = 1;
+    int64_t small_work = 512;
+    void* stream_v = nullptr;
+    SD_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
+    SD_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
+    if (left->device != device || right->device != device)
+        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: a geometry column of another device");
+    if (n_pairs == 0) return MOSAIC_OK;
+    tile = std::max(1, std::min(tile, kMaxTile));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int64_t n = n_pairs;
+
+    DevMem s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
+    PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
+    if (left_row) {
+        SD_RC(on_device(left_row, n, s_lrow, stream, &pa.lrow));
+        SD_RC(on_device(right_row, n, s_rrow, stream, &pa.rrow));
+    }
+    SD_HIP(s_plan.alloc((size_t)n * sizeof(int32_t)));
+    SD_HIP(s_list.alloc((size_t)n * sizeof(int64_t)));
+    SD_HIP(s_counts.alloc(4 * sizeof(unsigned long long)));
+    SD_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
+    pa.plan = (int32_t*)s_plan.p;
+    pa.list = (int64_t*)s_list.p;
+    pa.counts = (unsigned long long*)s_counts.p;
+    const int64_t wide = (int64_t)n_cu * 16;
+    hipLaunchKernelGGL(k_dist_plan, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa);
+    SD_HIP(hipGetLastError());
+    unsigned long long counts[4] = {0, 0, 0, 0};
+    SD_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    SD_HIP(hipStreamSynchronize(stream));
+    if (counts[2])
+        return mosaic_tess_fail(MOSAIC_E_ARG, ("st_distance: " + std::to_string(counts[2]) + " pair(s) name a row outside their column").c_str());
+
+    const bool dev_out = is_device_ptr(out), dev_status = !status || is_device_ptr(status);
+    double* d_out = out;
+    int32_t* d_status = status;
+    if (!dev_out) {
+        SD_HIP(s_out.alloc((size_t)n * sizeof(double)));
+        d_out = (double*)s_out.p;
+    }
+    if (!dev_status) {
+        SD_HIP(s_status.alloc((size_t)n * sizeof(int32_t)));
+        d_status = (int32_t*)s_status.p;
+    }
+    hipLaunchKernelGGL(k_dist_fill, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
+    SD_HIP(hipGetLastError());
+    DistArgs da{pa.L, pa.R, pa.lrow, pa.rrow, pa.list, (int64_t)counts[0], d_out, tile, prune};
+    if (counts[0]) {
+        hipLaunchKernelGGL(k_dist_small, dim3((unsigned)blocks_for((int64_t)counts[0], wide)), dim3(kBlock), 0, stream, da);
+        SD_HIP(hipGetLastError());
+    }
+    if (counts[1]) {
+        da.list = pa.list + (n - (int64_t)counts[1]);
+        da.n_list = (int64_t)counts[1];
+        hipLaunchKernelGGL(k_dist_block, dim3((unsigned)std::min<int64_t>(da.n_list, (int64_t)1 << 20)), dim3(kBlock), 0, stream, da);
+        SD_HIP(hipGetLastError());
+    }
+    if (!dev_out) SD_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (!dev_status) SD_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    SD_HIP(hipStreamSynchronize(stream));
+    return MOSAIC_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""Host-side geometry encoding helpers: WKB and WKT for (Multi)Polygons and Points.
+"""Host-side geometry encoding helpers: WKB and WKT for (Multi)Polygons and (Multi)Points.
 
 These mirror what the reference's JTS IO produces and consumes for the chip join's data contract:
 chip ``wkb`` is JTS ``WKBWriter`` output (2D, big-endian by default --
@@ -14,6 +14,7 @@ import struct
 
 WKB_POINT = 1
 WKB_POLYGON = 3
+WKB_MULTIPOINT = 4
 WKB_MULTIPOLYGON = 6
 
 
@@ -38,6 +39,13 @@ def geometry_wkb(parts, big_endian=True):
 def point_wkb(x, y, big_endian=True):
     bo = ">" if big_endian else "<"
     return struct.pack(bo + "BIdd", 0 if big_endian else 1, WKB_POINT, x, y)
+
+
+def multipoint_wkb(points, big_endian=True):
+    """MultiPoint of (x, y) tuples (JTS WKBWriter layout)."""
+    bo = ">" if big_endian else "<"
+    head = struct.pack(bo + "BII", 0 if big_endian else 1, WKB_MULTIPOINT, len(points))
+    return head + b"".join(point_wkb(x, y, big_endian) for x, y in points)
 
 
 def _read_geom(buf, pos):
@@ -66,6 +74,16 @@ def _read_geom(buf, pos):
             pos += 8 * dims * npts
             rings.append([(vals[dims * k], vals[dims * k + 1]) for k in range(npts)])
         return ("polygon", [rings]), pos
+    if t == WKB_MULTIPOINT:
+        (np_,) = struct.unpack_from(bo + "I", buf, pos)
+        pos += 4
+        pts = []
+        for _ in range(np_):
+            (kind, g), pos = _read_geom(buf, pos)
+            if kind != "point":
+                raise ValueError("MultiPoint member is not a Point")
+            pts.append(g)
+        return ("multipoint", pts), pos
     if t == WKB_MULTIPOLYGON:
         (np_,) = struct.unpack_from(bo + "I", buf, pos)
         pos += 4
@@ -80,7 +98,7 @@ def _read_geom(buf, pos):
 
 
 def read_wkb(buf):
-    """Returns ('point', (x, y)) or ('polygon', parts)."""
+    """Returns ('point', (x, y)), ('multipoint', [(x, y), ...]) or ('polygon', parts)."""
     g, _ = _read_geom(bytes(buf), 0)
     return g
 
@@ -100,12 +118,23 @@ def _parse_ring_list(txt):
 
 
 def read_wkt(text):
-    """Minimal WKT reader for POINT / POLYGON / MULTIPOLYGON (JTS WKTReader subset)."""
+    """Minimal WKT reader for POINT / MULTIPOINT / POLYGON / MULTIPOLYGON (JTS WKTReader subset)."""
     t = text.strip()
     head = t.split("(", 1)[0].strip().upper()
     if head.endswith("EMPTY") or t.upper().endswith("EMPTY"):
         kind = head.split()[0]
+        if kind == "MULTIPOINT":
+            return ("multipoint", [])
         return ("point", None) if kind == "POINT" else ("polygon", [])
+    if head == "MULTIPOINT":
+        # both of JTS's forms: MULTIPOINT ((1 2), (3 4)) and MULTIPOINT (1 2, 3 4)
+        inner = t[t.index("(") + 1:t.rindex(")")]
+        pts = []
+        for pair in inner.split(","):
+            nums = re.findall(_NUM, pair)
+            if nums:  # a member written EMPTY adds no coordinate
+                pts.append((float(nums[0]), float(nums[1])))
+        return ("multipoint", pts)
     if head == "POINT":
         nums = re.findall(_NUM, t)
         return ("point", (float(nums[0]), float(nums[1])))
