@@ -328,9 +328,14 @@ int mosaic_pip_join_pairs(mosaic_ctx* ctx, const mosaic_chips* chips, const doub
  * from its lowest vertex, shells counter-clockwise, holes clockwise, polygons by lowest vertex (the
  * order of the reference's rendered chips); a border chip equal to its cell is a core chip
  * (`intersect.equals(indexGeom)`).  A core chip's geometry is indexToGeometry(cell) (densify > 1: H3
- * core outlines follow the cell's arcs with `densify` points a side instead).  Cells the planar clip
- * cannot take (over the antimeridian or a pole) are clipped in the face plane instead
- * (mosaic_tess_counters counts them).  MOSAIC_E_ARG for a geometry with a vertex more than ~78 degrees
+ * core outlines follow the cell's arcs with `densify` points a side instead).
+ * Divergence from the reference: a cell the planar clip cannot take -- its h3ToGeoBoundary ring lies
+ * over the antimeridian (a side spanning more than 180 degrees of longitude) or a pole, so it is no
+ * polygon in the lon / lat plane -- gets the face-plane chip, not `geometry n indexToGeometry`: the
+ * geometry clipped against the cell's hexagon in the icosahedron face's gnomonic plane, computed
+ * vertices mapped back to lon / lat.  The reference intersects with the wrapped lon / lat ring there
+ * (a polygon spanning the globe's width), which is not restated.  mosaic_tess_counters counts these
+ * cells.  MOSAIC_E_ARG for a geometry with a vertex more than ~78 degrees
  * from the centre of a face it meets.
  * Reference: expressions/index/MosaicExplode.scala:70-79, core/Mosaic.scala:21-87,
  * core/index/IndexSystem.scala:152-186, core/index/H3IndexSystem.scala:93-100. */
@@ -357,7 +362,12 @@ int mosaic_chip_set_destroy(mosaic_chip_set* cs);
  * k_tess_classify_poly on the (densify-subdivided) hexagons in the icosahedron face plane.  Border
  * cells are clipped on the GPU as well (k_tess_clip_ll, one lane per cell, the host routine's
  * arithmetic); candidate enumeration, the per-face pieces of H3 geometries spanning faces and the
- * chip WKB assembly are host code.  Errors as mosaic_tessellate. */
+ * chip WKB assembly are host code.  A border cell the lane cannot take is clipped by
+ * mosaic_tessellate's host routine, with the same bytes: one needing more than the lane's workspace
+ * (24 ring chains, 12 result rings), one whose result does not fit the shared output buffer, and one
+ * that is no planar lon / lat polygon (over the antimeridian or a pole) -- the last gets the
+ * face-plane chip, mosaic_tessellate's divergence from the reference above, and is counted by
+ * mosaic_tess_counters in the same way.  Errors as mosaic_tessellate. */
 int mosaic_tessellate_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const int64_t* geom_parts,
                           const int64_t* part_rings, const int64_t* ring_offsets, const double* xy,
                           int keep_core_geom, int densify, mosaic_chip_set** out);

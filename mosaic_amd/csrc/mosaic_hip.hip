@@ -50,6 +50,7 @@
 #include "st_distance.h"
 #include "tess_clip.h"
 #include "tess_gpu.h"
+#include "tess_records.h"
 #include "tiles.h"
 
 using namespace mosaic;
@@ -5911,7 +5912,8 @@ static int run_clip_ll(ThreadCtx* c, ClipLLBufs& B, const void* d_gxy, const voi
     if ((rc = d2h(c, cnt, B.cnt.p, sizeof cnt))) return rc;
     if ((rc = d2h(c, out->status.data(), B.status.p, (size_t)n_tasks))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    // (counters past a cap: those tasks came back with status 1; the space before is valid)
+    // (the vertex counter past out_cap: those tasks came back with status 1 before they took ring or
+    // part slots, so every ring / part slot below its counter was written in this launch)
     const int64_t nv_out = std::min<int64_t>((int64_t)cnt[0], out_cap), nr = std::min<int64_t>((int64_t)cnt[1], ring_cap),
                   np = std::min<int64_t>((int64_t)cnt[2], part_cap);
     out->verts.resize((size_t)nv_out * 2);
@@ -5921,17 +5923,9 @@ static int run_clip_ll(ThreadCtx* c, ClipLLBufs& B, const void* d_gxy, const voi
     if (nr && (rc = d2h(c, out->rings.data(), B.rings.p, (size_t)nr * sizeof(tessclip::ClipRing)))) return rc;
     if (np && (rc = d2h(c, out->parts.data(), B.parts.p, (size_t)np * sizeof(tessclip::ClipPart)))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    // drop the records of tasks that went to the host (an overflowing task may have taken ring / part
-    // slots before its check failed: it wrote nothing into them)
-    {
-        std::vector<uint8_t> host(out->status.size());
-        std::unordered_map<int64_t, int64_t> pos;
-        for (int64_t t = 0; t < n_tasks; t++) pos[tasks[(size_t)t]] = t;
-        auto keep_ring = [&](const tessclip::ClipRing& r) { auto it = pos.find(r.cand); return it != pos.end() && out->status[(size_t)it->second] != 1; };
-        auto keep_part = [&](const tessclip::ClipPart& r) { auto it = pos.find(r.cand); return it != pos.end() && out->status[(size_t)it->second] != 1; };
-        out->rings.erase(std::remove_if(out->rings.begin(), out->rings.end(), [&](const tessclip::ClipRing& r) { return !keep_ring(r); }), out->rings.end());
-        out->parts.erase(std::remove_if(out->parts.begin(), out->parts.end(), [&](const tessclip::ClipPart& r) { return !keep_part(r); }), out->parts.end());
-    }
+    // drop the records of tasks that went to the host and check every kept one against verts; a task
+    // with a record that cannot be read goes to the host as well (tess_records.h)
+    (void)tessclip::filter_records(tasks, out);
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev.e[0], ev.e[1]);
     out->kernel_ms = ms;

@@ -12,8 +12,7 @@
 namespace mosaic {
 namespace tessll {
 
-// per-lane workspace (chains of the ring walks, result rings); a task needing more goes to the host
-static constexpr int kLLChains = 24, kLLOut = 12;
+// (per-lane workspace kLLChains / kLLOut: tess_gpu.h)
 
 struct ClipLLArgs {
     const double* gxy;  // the geometries' rings in output coordinates (lon / lat degrees, BNG metres)

@@ -62,11 +62,23 @@ __global__ void __launch_bounds__(256) k_tess_clip_ll(ClipLLArgs a) {
         }
         int64_t tot = 0;
         for (int32_t o = 0; o < w.n_out; o++) tot += w.out[o].npts + 1;
+        // Vertex space first: a task that does not fit goes to the host before it takes ring or part
+        // slots, so every slot below those two counters belongs to a task that writes it (the host
+        // copies all of them back, and the buffers keep an earlier launch's records).  The ring and
+        // part caps (kLLOut per task, polys <= n_out <= kLLOut) then cannot be exceeded; should they
+        // be, the slots taken below the caps are marked as nobody's.
         const unsigned long long off0 = atomicAdd(&a.counters[0], (unsigned long long)tot);
+        if ((int64_t)(off0 + tot) > a.out_cap) {
+            a.status[t] = 1;
+            continue;
+        }
         const unsigned long long rid = atomicAdd(&a.counters[1], (unsigned long long)w.n_out);
         const unsigned long long pid = atomicAdd(&a.counters[2], (unsigned long long)polys);
-        if ((int64_t)(off0 + tot) > a.out_cap || (int64_t)(rid + w.n_out) > a.ring_cap ||
-            (int64_t)(pid + polys) > a.part_cap) {
+        if ((int64_t)(rid + w.n_out) > a.ring_cap || (int64_t)(pid + polys) > a.part_cap) {
+            for (int64_t i = (int64_t)rid; i < (int64_t)(rid + w.n_out) && i < a.ring_cap; i++)
+                a.rings[i] = tessclip::ClipRing{-1, 0, 0, 0, 0, 0};
+            for (int64_t i = (int64_t)pid; i < (int64_t)(pid + polys) && i < a.part_cap; i++)
+                a.parts[i] = tessclip::ClipPart{-1, 0, 0};
             a.status[t] = 1;
             continue;
         }

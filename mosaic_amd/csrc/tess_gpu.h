@@ -9,6 +9,13 @@
 struct mosaic_ctx;
 
 namespace mosaic {
+namespace tessll {
+// k_tess_clip_ll's per-lane workspace (chains of the ring walks, result rings); a task needing more
+// goes to the host.  Here, not in tess_clip.h, so host-only code (g++) can size llclip::Work as the
+// device does; part of tess_clip.h's layout fingerprint.
+static constexpr int kLLChains = 24, kLLOut = 12;
+}  // namespace tessll
+
 namespace tessclip {
 
 struct ClipRing {  // one kept output ring (closed: n vertices, the first repeated last)

@@ -34,6 +34,7 @@
 
 #include "../../include/mosaic_hip.h"
 #include "tess_gpu.h"
+#include "tess_records.h"
 #include "bng_device.h"
 #include "h3_device.h"
 #include "h3_geom.h"
@@ -43,6 +44,7 @@
 #include <unordered_map>
 
 using namespace mosaic;
+using tessclip::ClippedChips;  // the GPU-clipped border chips by candidate (tess_records.h)
 
 extern "C" int mosaic_tess_fail(int code, const char* msg);  // defined in mosaic_hip.hip
 extern "C" int mosaic_tess_classify_bng(mosaic_ctx* c, int64_t n_geoms, const int64_t* geom_parts,
@@ -930,101 +932,6 @@ int tessellate_h3_multiface(mosaic_chip_set* cs, int32_t key, int res, int D, in
     multiface_emit(cs, key, res, keep_core_geom, mf, geo, gg);
     return MOSAIC_OK;
 }
-
-// The border chips the GPU clipped (tess_gpu.h), indexed by candidate: rings sorted by (candidate,
-// part, ring), parts by (candidate, part).
-struct ClippedChips {
-    tessclip::ClipResult r;
-    std::vector<int64_t> task_of;  // candidate -> task (-1: not a border task)
-    std::vector<int64_t> ring_at, part_at;  // candidate c's rings / parts: [ring_at[c], ring_at[c + 1])
-    void index(int64_t n_cand, const std::vector<int64_t>& tasks) {
-        // stable counting sort by candidate (the kernels append each candidate's rings / parts in
-        // (part, ring) order from one wave or lane; a candidate whose entries are not is sorted on
-        // its own), keeping each candidate's start
-        auto by_cand = [&](auto& v, auto less, std::vector<int64_t>& start) {
-            start.assign((size_t)n_cand + 1, 0);
-            for (auto& e : v) start[(size_t)e.cand + 1]++;
-            for (int64_t c = 0; c < n_cand; c++) start[(size_t)c + 1] += start[(size_t)c];
-            std::remove_reference_t<decltype(v)> out(v.size());
-            std::vector<int64_t> pos(start.begin(), start.end() - 1);
-            for (auto& e : v) out[(size_t)pos[(size_t)e.cand]++] = e;
-            for (int64_t c = 0; c < n_cand; c++) {
-                auto b = out.begin() + start[(size_t)c], e = out.begin() + start[(size_t)c + 1];
-                if (e - b > 1 && !std::is_sorted(b, e, less)) std::sort(b, e, less);
-            }
-            v.swap(out);
-        };
-        by_cand(r.rings, [](const tessclip::ClipRing& a, const tessclip::ClipRing& b) {
-            return a.part != b.part ? a.part < b.part : a.ring < b.ring;
-        }, ring_at);
-        by_cand(r.parts, [](const tessclip::ClipPart& a, const tessclip::ClipPart& b) { return a.part < b.part; }, part_at);
-        task_of.assign((size_t)n_cand, -1);
-        for (size_t t = 0; t < tasks.size(); t++) task_of[(size_t)tasks[t]] = (int64_t)t;
-    }
-    bool redo(int64_t k) const { return task_of[(size_t)k] < 0 || r.status[(size_t)task_of[(size_t)k]] == 1; }
-    bool is_cell(int64_t k) const { return task_of[(size_t)k] >= 0 && r.status[(size_t)task_of[(size_t)k]] == 2; }
-    // candidate k's clipped geometry as clip_cell's out_parts (kept parts with rings, closed rings)
-    void parts_of(int64_t k, Geo3& out) const {
-        out.clear();
-        size_t jr = (size_t)ring_at[(size_t)k];
-        for (size_t jp = (size_t)part_at[(size_t)k]; jp < r.parts.size() && r.parts[jp].cand == k; jp++) {
-            const int32_t part = r.parts[jp].part;
-            while (jr < r.rings.size() && r.rings[jr].cand == k && r.rings[jr].part < part) jr++;
-            const size_t r0 = jr;
-            while (jr < r.rings.size() && r.rings[jr].cand == k && r.rings[jr].part == part) jr++;
-            if (!r.parts[jp].keep || jr == r0) continue;
-            std::vector<std::vector<P2>> rings;
-            for (size_t q = r0; q < jr; q++) {
-                const tessclip::ClipRing& cr = r.rings[q];
-                std::vector<P2> ring((size_t)cr.n);
-                for (int32_t v = 0; v < cr.n; v++) ring[(size_t)v] = {r.verts[2 * (cr.off + v)], r.verts[2 * (cr.off + v) + 1]};
-                rings.push_back(std::move(ring));
-            }
-            out.push_back(std::move(rings));
-        }
-    }
-    // candidate k's chip as WKB appended to w (to_wkb's bytes); false (nothing written): no chip
-    template <class W>
-    bool chip(int64_t k, W& w) const {
-        const size_t ir = (size_t)ring_at[(size_t)k], ip = (size_t)part_at[(size_t)k];
-        // the kept parts that have rings: (first ring, ring count)
-        std::pair<size_t, size_t> kept[64];
-        std::vector<std::pair<size_t, size_t>> more;
-        size_t n_kept = 0, jr = ir;
-        for (size_t jp = ip; jp < r.parts.size() && r.parts[jp].cand == k; jp++) {
-            const int32_t part = r.parts[jp].part;
-            while (jr < r.rings.size() && r.rings[jr].cand == k && r.rings[jr].part < part) jr++;
-            const size_t r0 = jr;
-            while (jr < r.rings.size() && r.rings[jr].cand == k && r.rings[jr].part == part) jr++;
-            if (!r.parts[jp].keep || jr == r0) continue;
-            if (n_kept < 64) kept[n_kept] = {r0, jr - r0};
-            else more.push_back({r0, jr - r0});
-            n_kept++;
-        }
-        if (n_kept == 0) return false;
-        auto part_at = [&](size_t i) { return i < 64 ? kept[i] : more[i - 64]; };
-        if (n_kept > 1) {
-            w.u8(0);
-            w.u32(6);
-            w.u32((uint32_t)n_kept);
-        }
-        for (size_t i = 0; i < n_kept; i++) {
-            const auto pr = part_at(i);
-            w.u8(0);
-            w.u32(3);
-            w.u32((uint32_t)pr.second);
-            for (size_t q = pr.first; q < pr.first + pr.second; q++) {
-                const tessclip::ClipRing& cr = r.rings[q];
-                w.u32((uint32_t)cr.n);
-                for (int32_t v = 0; v < cr.n; v++) {
-                    w.f64(r.verts[2 * (cr.off + v)]);
-                    w.f64(r.verts[2 * (cr.off + v) + 1]);
-                }
-            }
-        }
-        return true;
-    }
-};
 
 // The face-spanning geometries' chips on the device (mosaic_tessellate_gpu): per-face pieces made on
 // host threads (multiface_pieces), then classified by one session over virtual geometries --

@@ -14,7 +14,7 @@ import pytest
 
 import oracle
 from mosaic_amd import MosaicContext
-from mosaic_amd.context import tessellate
+from mosaic_amd.context import tessellate, tessellate_counters
 from mosaic_amd.data import PolygonSet
 
 pytestmark = pytest.mark.gpu
@@ -100,10 +100,17 @@ def test_h3_gpu_tessellation_equals_host(ctx, res, densify):
     t0 = time.perf_counter()
     host = tessellate("H3", polys, res, densify=densify)
     t1 = time.perf_counter()
+    before = tessellate_counters()
     gpu = tessellate("H3", polys, res, densify=densify, ctx=ctx)
+    after = tessellate_counters()
     t2 = time.perf_counter()
     _same(host, gpu)
     assert host["is_core"].sum() > 0 and (host["is_core"] == 0).sum() > 0
+    if res < 10:
+        # every border chip of the zones was clipped on the device: the host clipped none in the GPU
+        # call and no cell fell back to the face-plane clip (tests/test_clip_caps.py: all these cells
+        # fit the lane's workspace)
+        assert (after[0] - before[0], after[1] - before[1]) == (0, 0)
     from mosaic_amd import _native as N
 
     ms = N.lib().mosaic_tess_last_classify_ms(ctx.handle)
@@ -183,19 +190,24 @@ def test_h3_gpu_tessellation_holes_multipart_duplicates(ctx, res, densify):
 
 
 def test_gpu_tessellation_small_rings_lane_kernel(ctx):
-    """Building-scale inputs go to k_tess_clip_lane (one lane per border cell: every ring <= 24
-    vertices, clip polygon <= 12 vertices); rings beyond that, or a densified hexagon of 18 sides,
-    to the wave kernel -- both must give the host producer's chip set byte for byte."""
+    """Building-scale inputs (tens of thousands of border cells, every ring a few vertices) through
+    k_tess_clip_ll, one lane per border cell, at several resolutions and densified hexagons, H3 (cell
+    polygons from the ids) and BNG (explicit squares): the host producer's chip set byte for byte,
+    and at H3 (11, 1) every border chip clipped on the device."""
     from mosaic_amd.data import synthetic_buildings
 
     bld = synthetic_buildings(20_000)
     for res, densify in ((11, 1), (12, 2), (11, 3)):
         host = tessellate("H3", bld, res, densify=densify)
+        before = tessellate_counters()
         gpu = tessellate("H3", bld, res, densify=densify, ctx=ctx)
+        after = tessellate_counters()
         _same(host, gpu)
         assert (host["is_core"] == 0).sum() > 10_000
+        if (res, densify) == (11, 1):  # no host redo, no fallback
+            assert (after[0] - before[0], after[1] - before[1]) == (0, 0)
     # BNG (clip squares, mode 1): small random polygons in London metres at 10 m cells, some with
-    # more than 24 vertices (wave kernel) beside the small ones
+    # more than 24 vertices beside the small ones
     rng = np.random.default_rng(11)
     rings = []
     for i in range(3000):
