@@ -555,6 +555,48 @@ int mosaic_geoms_destroy(mosaic_geoms* geoms);
 int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
                        const int64_t* right_row, int64_t n_pairs, double* out, int32_t* status);
 
+/* ---- GridRingNeighbours: one iteration of the KNN model (models/knn/GridRingNeighbours.scala:121-160) ---- */
+/* The candidates' chips as a map from a cell to its sorted, distinct candidate rows: built once per chip
+ * set on the GPU, immutable afterwards and usable from any thread, freed with
+ * mosaic_cell_index_destroy.  Chip i is (index_id[i], key[i] = its candidate row >= 0): the rows of
+ * grid_tessellateexplode(keepCoreGeometries = false), or one chip per point (Mosaic.pointChip).
+ * index_id / key: host or device pointers; at most 2^31 - 1 chips.  A negative key: MOSAIC_E_ARG. */
+typedef struct mosaic_cell_index mosaic_cell_index;
+int mosaic_cell_index_create(mosaic_ctx* ctx, int64_t n_chips, const int64_t* index_id, const int32_t* key,
+                             mosaic_cell_index** out);
+/* distinct cells, distinct (cell, candidate) entries, the largest number of candidates in one cell (any may be null) */
+int mosaic_cell_index_info(const mosaic_cell_index* index, int64_t* n_cells, int64_t* n_entries, int64_t* max_per_cell);
+int mosaic_cell_index_destroy(mosaic_cell_index* index);
+/* Row i says that cell[i] belongs to landmark left_row[i] (grid_geometrykringexplode(l, res, 1) in the
+ * model's first iteration, grid_geometrykloopexplode(l, res, it) afterwards; duplicate rows allowed;
+ * host or device pointers).  The result holds
+ *   the pairs: the set of (l, c) such that a given cell of l is the cell of a chip of c, without self
+ *     matches unless keep_self -- (l, c) is a self match iff both rows are MOSAIC_ROW_OK and have
+ *     identical flat content (the same parts, part kinds and rings, bitwise-equal vertices: an exact
+ *     comparison where the reference compares hashes) -- each with distance =
+ *     mosaic_st_distance(left[l], right[c]) (NaN where either row is not MOSAIC_ROW_OK: such a pair is
+ *     never a self match and sorts after the landmark's numbers), ordered by (l, distance bits, c):
+ *     ties by candidate row;
+ *   unmatched[l] = 1 iff a given cell of l is the cell of no chip (the left-outer join's null row).
+ * The reference's st_intersects_aggregate filter is always true in this join (the left chips are core
+ * chips) and is not evaluated.  The rows are those of the sequential definition in
+ * mosaic_amd/csrc/ring_neighbours.h.  Every size comes from a count pass: nothing is truncated.
+ * Errors, with nothing written: MOSAIC_E_ARG for a landmark row outside `left`, an index naming a row
+ * outside `right`, or 2^31 or more rows; MOSAIC_E_CAPACITY for 2^31 or more (landmark, candidate) hits
+ * before de-duplication in one call. */
+typedef struct mosaic_neighbours mosaic_neighbours;
+int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, const mosaic_geoms* left,
+                           const mosaic_geoms* right, const int64_t* left_row, const int64_t* cell, int64_t n,
+                           int keep_self, mosaic_neighbours** out);
+int mosaic_neighbours_info(const mosaic_neighbours* nb, int64_t* n_pairs, int64_t* n_left);
+/* left_row[n_pairs], right_row[n_pairs], distance[n_pairs], unmatched[n_left] (any may be null; host or device) */
+int mosaic_neighbours_export(const mosaic_neighbours* nb, int64_t* left_row, int64_t* right_row, double* distance,
+                             uint8_t* unmatched);
+int mosaic_neighbours_destroy(mosaic_neighbours* nb);
+/* Device time (HIP events on the calling thread's stream) of the calling thread's last
+ * mosaic_ring_neighbours, ms; split3 (nullable): probe + de-duplication + self-match filter, distance, order. */
+double mosaic_ring_neighbours_last_ms(double* split3);
+
 /* getBufferRadius(geometry, res) per geometry (the radius mosaicFill buffers by, core/Mosaic.scala:68):
  * H3 (H3IndexSystem.scala:73-80): the largest distance (degrees) from the centroid of the cell
  * holding the geometry's JTS centroid (its indexToGeometry polygon's JTS centroid) to that polygon's

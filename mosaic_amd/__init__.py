@@ -6,6 +6,7 @@ include/mosaic_hip.h; this package is the host-side mirror of the reference's fu
 from ._native import IllegalStateException, MosaicError, NativeUnavailable  # noqa: F401
 from .context import (BNGIndexSystem, ChipTable, GeometryTable, H3IndexSystem, MosaicContext,  # noqa: F401
                       RowPathRequired)
+from .knn import CellIndex, SpatialKNN  # noqa: F401
 
-__all__ = ["MosaicContext", "ChipTable", "GeometryTable", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
+__all__ = ["MosaicContext", "ChipTable", "GeometryTable", "CellIndex", "SpatialKNN", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
            "MosaicError", "NativeUnavailable"]

@@ -46,6 +46,8 @@ EXPORTS = [
     "mosaic_isect_geoms_destroy", "mosaic_chips_kring", "mosaic_geometry_kring", "mosaic_cell_lists_export_dist",
     "mosaic_geometry_kring_last_ms", "mosaic_geoms_create_wkb", "mosaic_geoms_create_arrays",
     "mosaic_geoms_create_points", "mosaic_geoms_info", "mosaic_geoms_destroy", "mosaic_st_distance",
+    "mosaic_cell_index_create", "mosaic_cell_index_info", "mosaic_cell_index_destroy", "mosaic_ring_neighbours",
+    "mosaic_neighbours_info", "mosaic_neighbours_export", "mosaic_neighbours_destroy", "mosaic_ring_neighbours_last_ms",
 ]
 
 GEOM_WKB = 0
@@ -161,6 +163,14 @@ def lib():
         "mosaic_geoms_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_geoms_destroy": ([vp], i32),
         "mosaic_st_distance": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
+        "mosaic_cell_index_create": ([vp, i64, vp, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_cell_index_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "mosaic_cell_index_destroy": ([vp], i32),
+        "mosaic_ring_neighbours": ([vp, vp, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_neighbours_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "mosaic_neighbours_export": ([vp, vp, vp, vp, vp], i32),
+        "mosaic_neighbours_destroy": ([vp], i32),
+        "mosaic_ring_neighbours_last_ms": ([vp], ctypes.c_double),
         "mosaic_buffer_radius": ([vp, i32, i32, i64, vp, vp, vp, vp, vp], i32),
         "mosaic_chip_table_create_arrays": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_intersection_aggregate": ([vp, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),

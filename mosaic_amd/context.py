@@ -781,6 +781,21 @@ class MosaicContext:
             raise RowPathRequired(path)
         return out
 
+    # ---- the KNN model (mosaic_amd/knn.py) ----
+    def cell_index(self, chips):
+        """A ``CellIndex``: the candidates' chips as a device-resident map from a cell to its candidate
+        rows, built once and probed by every ``grid_ring_neighbours`` call (see ``knn.CellIndex``)."""
+        from .knn import CellIndex
+
+        return CellIndex(self, chips)
+
+    def grid_ring_neighbours(self, landmarks, candidates, cell_index, rows, cells, keep_self=False):
+        """One iteration of the reference's KNN model (models/knn/GridRingNeighbours.scala:121-160):
+        ``(landmark_row, candidate_row, distance, unmatched)``; see ``knn.grid_ring_neighbours``."""
+        from .knn import grid_ring_neighbours
+
+        return grid_ring_neighbours(self, landmarks, candidates, cell_index, rows, cells, keep_self)
+
     # ---- the chip join ----
     def grid_tessellateexplode(self, polygons, resolution, keep_core_geom=True, densify=1):
         """grid_tessellateexplode(geom, res, keepCoreGeom) (MosaicContext.scala functions ->

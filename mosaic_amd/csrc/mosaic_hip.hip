@@ -47,6 +47,7 @@
 #include "point_decode.h"
 #include "raster.h"
 #include "raster_build.h"
+#include "ring_neighbours.h"
 #include "st_distance.h"
 #include "tess_clip.h"
 #include "tess_gpu.h"
@@ -89,6 +90,7 @@ extern "C" uint64_t mosaic_layout_join_binned(void);
 extern "C" uint64_t mosaic_layout_join_stream(void);
 extern "C" uint64_t mosaic_layout_tess_clip(void);
 extern "C" uint64_t mosaic_layout_st_distance(void);
+extern "C" uint64_t mosaic_layout_ring_neighbours(void);
 
 template <int GRID, bool LDS_COUNTS, bool PAIRS>
 __global__ void __launch_bounds__(256) k_join_raster(JoinArgs a) {
@@ -2532,7 +2534,8 @@ int mosaic_init(int device, mosaic_ctx** out) {
     // would pass structs with shifted fields between translation units: refuse to run
     if (mosaic_layout_join_binned() != mosaic_layout_fingerprint() || mosaic_layout_join_stream() != mosaic_layout_fingerprint() ||
         mosaic_layout_tess_clip() != mosaic::tessll::layout_fingerprint() ||
-        mosaic_layout_st_distance() != mosaic::dist::layout_fingerprint())
+        mosaic_layout_st_distance() != mosaic::dist::layout_fingerprint() ||
+        mosaic_layout_ring_neighbours() != mosaic::rn::layout_fingerprint())
         return fail(MOSAIC_E_ARG, "libmosaic_hip.so links objects built against different struct layouts (rebuild every object)");
     thp_off_once();
     int count = 0;

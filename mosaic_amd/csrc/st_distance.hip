@@ -33,31 +33,13 @@
 
 #include "../../include/mosaic_hip.h"
 #include "geoms_build.h"
+#include "geoms_device.h"
 #include "st_distance.h"
 
 using namespace mosaic;
 
 extern "C" int mosaic_tess_fail(int code, const char* msg);
 extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune);
-
-struct mosaic_geoms {
-    int device = 0;
-    int64_t n_geoms = 0, n_vertices = 0, n_row_path = 0;
-    pip::Vec2* verts = nullptr;
-    uint32_t* ring_start = nullptr;
-    pip::Box* ring_bbox = nullptr;
-    uint32_t* part_ring = nullptr;
-    uint8_t* part_kind = nullptr;
-    uint32_t* geom_part = nullptr;
-    pip::Box* geom_bbox = nullptr;
-    uint32_t* geom_facets = nullptr;
-    int32_t* row_status = nullptr;
-    ~mosaic_geoms() {
-        for (void* p : {(void*)verts, (void*)ring_start, (void*)ring_bbox, (void*)part_ring, (void*)part_kind,
-                        (void*)geom_part, (void*)geom_bbox, (void*)geom_facets, (void*)row_status})
-            if (p) (void)hipFree(p);
-    }
-};
 
 namespace {
 
@@ -90,23 +72,8 @@ Col view(const mosaic_geoms* g) {
                g->part_kind, g->geom_facets, g->row_status, g->n_geoms};
 }
 
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-};
-
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
+using dev::DevMem;
+using dev::is_device_ptr;
 
 __device__ inline unsigned long long wave_append(unsigned long long* counter, bool pred) {
     const unsigned long long m = __ballot(pred);
@@ -374,19 +341,6 @@ int upload_column(int device, const GeomColumn& c, mosaic_geoms** out) {
     return MOSAIC_OK;
 }
 
-// src (n elements, host or device) as a device pointer; a host array is copied into `stage`
-template <class T>
-int on_device(const T* src, int64_t n, DevMem& stage, hipStream_t stream, const T** out) {
-    if (is_device_ptr(src)) {
-        *out = src;
-        return MOSAIC_OK;
-    }
-    SD_HIP(stage.alloc((size_t)n * sizeof(T)));
-    SD_HIP(hipMemcpyAsync(stage.p, src, (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
-    *out = (const T*)stage.p;
-    return MOSAIC_OK;
-}
-
 int64_t blocks_for(int64_t n, int64_t cap) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
 
 }  // namespace
@@ -452,8 +406,8 @@ int mosaic_geoms_create_points(mosaic_ctx* ctx, const double* x, const double* y
     DevMem sx, sy, cnt;
     const double *dx = nullptr, *dy = nullptr;
     if (n > 0) {
-        SD_RC(on_device(x, n, sx, stream, &dx));
-        SD_RC(on_device(y, n, sy, stream, &dy));
+        SD_HIP(dev::on_device(x, n, sx, stream, &dx));
+        SD_HIP(dev::on_device(y, n, sy, stream, &dy));
     }
     SD_HIP(cnt.alloc(sizeof(unsigned long long)));
     SD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), stream));
@@ -507,8 +461,8 @@ int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_g
     DevMem s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
     PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
     if (left_row) {
-        SD_RC(on_device(left_row, n, s_lrow, stream, &pa.lrow));
-        SD_RC(on_device(right_row, n, s_rrow, stream, &pa.rrow));
+        SD_HIP(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
+        SD_HIP(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
     }
     SD_HIP(s_plan.alloc((size_t)n * sizeof(int32_t)));
     SD_HIP(s_list.alloc((size_t)n * sizeof(int64_t)));
