@@ -377,6 +377,45 @@ double mosaic_tess_last_classify_ms(const mosaic_ctx* ctx);
  * that fell back to the face-plane clip (ll_fallbacks). */
 int mosaic_tess_counters(int64_t* ll_chips, int64_t* ll_fallbacks);
 
+/* ---- grid_tessellateexplode for LineString / MultiLineString (Mosaic.lineFill) ---- */
+/* Chips of line geometries (core/Mosaic.scala:89-97, 146-194): geometry g is the component lines
+ * [geom_lines[g], geom_lines[g + 1]) and line l the vertices xy[2 line_offsets[l] .. 2 line_offsets[l + 1])
+ * (host arrays; x = lon, y = lat for H3, BNG metres).  Each component is decomposed on its own (the
+ * reference flattens a MultiLineString), so a cell two components meet gives two rows.  Consecutive
+ * repeated vertices are removed first; a component without vertices gives no chips, one of a single
+ * distinct vertex MOSAIC_E_ARG, a NaN coordinate MOSAIC_E_NAN.
+ * One row per (component, cell whose closed indexToGeometry polygon the line meets) -- the cells the
+ * reference's lineDecompose traversal reaches -- with is_core = 0, key = g and the WKB (JTS WKBWriter,
+ * big-endian 2D) of line n cell after JTS's overlay of a line with an area: the line cut where it meets
+ * the cell's boundary (the polygon producer's crossing arithmetic: llclip.h), the pieces inside or on the
+ * cell kept, each a LineString in the line's direction with original vertices copied; one piece:
+ * LINESTRING, several: MULTILINESTRING in line order; a cell the line only touches: POINT / MULTIPOINT
+ * of the distinct contact points in line order.  A piece along a cell side belongs to both cells.
+ * Rows are ordered by geometry, component, then the position along the line where the chip begins (ties
+ * by cell id): the reference's breadth-first order is a Spark row order and is not restated.  The piece
+ * order and direction are derived from JTS's algorithm; no JTS output pins them.
+ * Divergences from the reference: (a) a cell holding both pieces and isolated contact points gives the
+ * pieces (the reference's GeometryCollection collapses to POLYGON EMPTY: it drops the chip and stops
+ * expanding there, which can lose the rest of the line); (b) the line is not noded at its own crossings
+ * (the same point set in fewer, longer pieces); (c) a cell the walk comes to that is no planar lon / lat
+ * polygon (over the antimeridian or a pole), or a vertex outside the grid: MOSAIC_E_ARG naming the
+ * geometry.  keep_core_geom does not exist for lines (the reference ignores it).
+ * cells_only = 1: the same rows with an empty WKB column (what the k-rings need). */
+int mosaic_tessellate_lines(int grid, int res, int64_t n_geoms, const int64_t* geom_lines, const int64_t* line_offsets,
+                            const double* xy, int cells_only, mosaic_chip_set** out);
+/* The same chip set, row for row and byte for byte, produced on the GPU: k_line_spans splits every
+ * segment into spans of about two cells; k_line_walk (one lane per span, count then write) emits the
+ * (cell, segment) pairs of exact walks; a radix sort groups them by (cell, line); k_line_clip (one lane
+ * per group, count then write) builds each chip's pieces into space taken by a prefix sum; the host
+ * orders the rows and writes the WKB.  A span trying more than 64 cells and a chip of more than 8 pieces
+ * are handed to the host routine (same bytes). */
+int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const int64_t* geom_lines,
+                                const int64_t* line_offsets, const double* xy, int cells_only, mosaic_chip_set** out);
+/* The calling thread's last mosaic_tessellate_lines_gpu: out = segments walked, (line, cell) groups,
+ * groups handed to the host, (cell, segment) pairs emitted; ms = device time (HIP events) of the walk
+ * (spans included), the sort (grouping included) and the clip. */
+int mosaic_tess_lines_last(int64_t out[4], double ms[3]);
+
 /* ---- st_contains per row ---- */
 /* out[i] = JTS contains(geometry[geom_index[i]], POINT(px[i] py[i])); geometries given as WKB. */
 int mosaic_st_contains(mosaic_ctx* ctx, int64_t n_geoms, const int64_t* wkb_offsets, const uint8_t* wkb,
@@ -505,8 +544,9 @@ double mosaic_polyfill_last_ms(void);
  * mosaic_chips_kring takes chip columns (the rows of grid_tessellateexplode, or one non-core chip per
  * point: Mosaic.pointChip): key[i] in [0, n_geoms) names the chip's geometry, duplicate rows are
  * allowed, a cell given both as core and as border counts as both.  mosaic_geometry_kring is
- * mosaic_tessellate_gpu(keep_core_geom = 0) followed by it.  Line geometries are not served (the
- * engine has no lineFill).  status[g]: MOSAIC_POLYFILL_UNSUPPORTED (no cells) for a geometry with a
+ * mosaic_tessellate_gpu(keep_core_geom = 0) followed by it; for line geometries
+ * the binding runs mosaic_tessellate_lines_gpu(cells_only = 1) and passes its rows, all border chips,
+ * to mosaic_chips_kring.  status[g]: MOSAIC_POLYFILL_UNSUPPORTED (no cells) for a geometry with a
  * chip id that is not a valid cell of res; a geometry without chips gives an empty row.
  * Options: "gk_table_log2" (log2 of the search table's first slot count, 4..30, default 16; the
  * table grows by rehashing), "gk_max_cells" (slot count past which the call returns

@@ -48,6 +48,7 @@ EXPORTS = [
     "mosaic_geoms_create_points", "mosaic_geoms_info", "mosaic_geoms_destroy", "mosaic_st_distance",
     "mosaic_cell_index_create", "mosaic_cell_index_info", "mosaic_cell_index_destroy", "mosaic_ring_neighbours",
     "mosaic_neighbours_info", "mosaic_neighbours_export", "mosaic_neighbours_destroy", "mosaic_ring_neighbours_last_ms",
+    "mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last",
 ]
 
 GEOM_WKB = 0
@@ -139,6 +140,9 @@ def lib():
         "mosaic_cell_boundary_wkb": ([vp, i32, vp, vp, i64, vp], i32),
         "mosaic_h3_cell_geometry": ([vp, i32, vp, vp, i64, vp, vp], i32),
         "mosaic_tessellate_gpu": ([vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_tessellate_lines": ([i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_tessellate_lines_gpu": ([vp, i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_tess_lines_last": ([vp, vp], i32),
         "mosaic_tess_last_classify_ms": ([vp], ctypes.c_double),
         "mosaic_tess_counters": ([ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_point_to_cell_exact": ([vp, i32, vp, vp, i64, vp], i32),

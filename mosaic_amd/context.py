@@ -797,7 +797,7 @@ class MosaicContext:
         return grid_ring_neighbours(self, landmarks, candidates, cell_index, rows, cells, keep_self)
 
     # ---- the chip join ----
-    def grid_tessellateexplode(self, polygons, resolution, keep_core_geom=True, densify=1):
+    def grid_tessellateexplode(self, polygons, resolution, keep_core_geom=True, densify=1, cells_only=False):
         """grid_tessellateexplode(geom, res, keepCoreGeom) (MosaicContext.scala functions ->
         MosaicExplode.scala:70-79 -> Mosaic.getChips core/Mosaic.scala:21-87) over a PolygonSet:
         chip columns (is_core, index_id, polygon_key, wkb) with the cell classification on this
@@ -805,8 +805,13 @@ class MosaicContext:
 
         H3 geometries spanning icosahedron faces are cut into per-face pieces; only a
         geometry with a vertex more than ~78 degrees from the centre of a face it meets (no gnomonic
-        face plane holds it) raises MosaicError (MOSAIC_E_ARG)."""
-        return tessellate(self.index_system, polygons, resolution, keep_core_geom, densify, ctx=self)
+        face plane holds it) raises MosaicError (MOSAIC_E_ARG).
+
+        A LineSet (LineString / MultiLineString rows) takes Mosaic.lineFill on this context's GPU
+        (mosaic_tessellate_lines_gpu): LINESTRING / MULTILINESTRING chips of the pieces of each
+        component line inside a cell, POINT / MULTIPOINT chips where it only touches one; a line that
+        comes to a cell over the antimeridian or a pole raises MosaicError (MOSAIC_E_ARG)."""
+        return tessellate(self.index_system, polygons, resolution, keep_core_geom, densify, ctx=self, cells_only=cells_only)
 
     def chip_table(self, is_core, index_id, wkb_list, polygon_key, resolution, n_polygons=None):
         """Build side: rows of grid_tessellateexplode output (MosaicExplode.scala:70-79)."""
@@ -922,6 +927,10 @@ class MosaicContext:
                                                   N.ptr(geoms.part_rings), N.ptr(geoms.ring_offsets),
                                                   N.ptr(geoms.xy), int(k), int(loop), ctypes.byref(h)))
         else:
+            if hasattr(geoms, "geom_lines"):  # a LineSet: its line chips' cells, all border chips
+                chips = tessellate(self.index_system, geoms, resolution, ctx=self, cells_only=True)
+                geoms = dict(is_core=chips["is_core"], index_id=chips["index_id"], polygon_key=chips["polygon_key"],
+                             n_geoms=len(geoms))
             if isinstance(geoms, dict):  # chip columns
                 is_core = np.ascontiguousarray(geoms["is_core"], np.uint8)
                 ids = np.ascontiguousarray(geoms["index_id"], np.int64)
@@ -976,8 +985,9 @@ class MosaicContext:
         ``geoms``: a PolygonSet; the chip columns ``tessellate`` / ``grid_tessellateexplode`` return
         (a dict, optionally with ``n_geoms``; MultiPoint rows are chips sharing a key, one non-core
         chip per point); or a point column in any form ``grid_pointascellid`` accepts (each row's cell
-        is one border chip, Mosaic.pointChip).  Line geometries are not served (no lineFill here): a
-        point column holding one raises RowPathRequired.
+        is one border chip, Mosaic.pointChip); or a LineSet, whose line chips (Mosaic.lineFill on the
+        GPU, cells only) are all border chips.  A line row inside a point column still raises
+        RowPathRequired.
 
         Returns one array of cells per geometry -- BNG ids as the reference's strings unless raw --
         in Scala 2.12 immutable HashSet iteration order (the reference returns a Set[Long]; equal
@@ -1155,11 +1165,14 @@ class MosaicContext:
             return lk[:k], rk[:k], ar[:k], st[:k]
 
 
-def tessellate(index_system, polygons, resolution, keep_core_geom=True, densify=1, ctx=None):
-    """grid_tessellateexplode over a PolygonSet (mosaic_amd.data.PolygonSet).
+def tessellate(index_system, polygons, resolution, keep_core_geom=True, densify=1, ctx=None, cells_only=False):
+    """grid_tessellateexplode over a PolygonSet or a LineSet (mosaic_amd.data).
 
     ctx=None: the host producer (mosaic_tessellate).  ctx=MosaicContext: the cell classification
     runs on the context's GPU (mosaic_tessellate_gpu), same chip set row for row.
+    A LineSet takes Mosaic.lineFill (mosaic_tessellate_lines / mosaic_tessellate_lines_gpu): one
+    non-core chip per (component line, cell the line meets), rows in line order; keep_core_geom and
+    densify do not apply, and cells_only=True leaves the wkb column empty.
 
     Returns chip columns: dict(is_core uint8, index_id int64, polygon_key int32 (geometry index),
     wkb=(offsets int64[n+1], data uint8[...])).  MosaicExplode.scala:70-79 / Mosaic.scala:21-87.
@@ -1168,7 +1181,14 @@ def tessellate(index_system, polygons, resolution, keep_core_geom=True, densify=
         index_system = INDEX_SYSTEMS[index_system]()
     res = index_system.get_resolution(resolution)
     h = ctypes.c_void_p()
-    if ctx is not None:
+    if hasattr(polygons, "geom_lines"):  # a LineSet: Mosaic.lineFill (keep_core_geom does not exist there)
+        args = (index_system.grid, res, len(polygons), N.ptr(polygons.geom_lines), N.ptr(polygons.line_offsets),
+                N.ptr(polygons.xy), int(bool(cells_only)), ctypes.byref(h))
+        if ctx is not None:
+            N.check(N.lib().mosaic_tessellate_lines_gpu(ctx.handle, *args))
+        else:
+            N.check(N.lib().mosaic_tessellate_lines(*args))
+    elif ctx is not None:
         N.check(N.lib().mosaic_tessellate_gpu(ctx.handle, index_system.grid, res, len(polygons),
                                               N.ptr(polygons.geom_parts), N.ptr(polygons.part_rings),
                                               N.ptr(polygons.ring_offsets), N.ptr(polygons.xy),

@@ -78,6 +78,60 @@ class PolygonSet:
         return float(v[:, 0].mean()), float(v[:, 1].mean())
 
 
+class LineSet:
+    """Line geometries as flat arrays: xy[V,2], line_offsets[L+1] (line l = vertices
+    [line_offsets[l], line_offsets[l+1])), geom_lines[G+1] (geometry g = the component lines
+    [geom_lines[g], geom_lines[g+1])): a LineString has one component, a MultiLineString several."""
+
+    def __init__(self, xy, line_offsets, geom_lines):
+        self.xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        self.line_offsets = np.ascontiguousarray(line_offsets, np.int64)
+        self.geom_lines = np.ascontiguousarray(geom_lines, np.int64)
+
+    @classmethod
+    def from_lines(cls, geoms):
+        """geoms: per geometry a list of component lines, each a sequence of (x, y)."""
+        xy, lo, gl = [], [0], [0]
+        for lines in geoms:
+            for ln in lines:
+                xy.extend((float(x), float(y)) for x, y in ln)
+                lo.append(len(xy))
+            gl.append(len(lo) - 1)
+        return cls(np.asarray(xy, np.float64).reshape(-1, 2), lo, gl)
+
+    @classmethod
+    def _from_parsed(cls, parsed):
+        for kind, _ in parsed:
+            if kind != "linestring":
+                raise ValueError(f"LineSet takes LINESTRING / MULTILINESTRING rows, found {kind}")
+        return cls.from_lines([g for _, g in parsed])
+
+    @classmethod
+    def from_wkt(cls, rows):
+        return cls._from_parsed([W.read_wkt(t) for t in rows])
+
+    @classmethod
+    def from_wkb(cls, rows):
+        return cls._from_parsed([W.read_wkb(b) for b in rows])
+
+    def __len__(self):
+        return len(self.geom_lines) - 1
+
+    def lines(self, g):
+        """Geometry g as a list of component lines, each a list of (x, y)."""
+        out = []
+        for l in range(self.geom_lines[g], self.geom_lines[g + 1]):
+            a, b = self.line_offsets[l], self.line_offsets[l + 1]
+            out.append([(float(x), float(y)) for x, y in self.xy[a:b]])
+        return out
+
+    def wkb(self, g, big_endian=True):
+        lines = self.lines(g)
+        if len(lines) == 1:
+            return W.linestring_wkb(lines[0], big_endian)
+        return W.multilinestring_wkb(lines, big_endian)
+
+
 def quickstart_points(zones, n, config=1, sigma=0.005, seed=None, round_1e6=True):
     """C1 / C3 mixture on the host (numpy PCG64)."""
     rng = np.random.Generator(np.random.PCG64(SEED_BASE + config if seed is None else seed))

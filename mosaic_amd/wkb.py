@@ -1,4 +1,5 @@
-"""Host-side geometry encoding helpers: WKB and WKT for (Multi)Polygons and (Multi)Points.
+"""Host-side geometry encoding helpers: WKB and WKT for (Multi)Polygons, (Multi)Points and
+(Multi)LineStrings.
 
 These mirror what the reference's JTS IO produces and consumes for the chip join's data contract:
 chip ``wkb`` is JTS ``WKBWriter`` output (2D, big-endian by default --
@@ -13,8 +14,10 @@ import re
 import struct
 
 WKB_POINT = 1
+WKB_LINESTRING = 2
 WKB_POLYGON = 3
 WKB_MULTIPOINT = 4
+WKB_MULTILINESTRING = 5
 WKB_MULTIPOLYGON = 6
 
 
@@ -48,6 +51,20 @@ def multipoint_wkb(points, big_endian=True):
     return head + b"".join(point_wkb(x, y, big_endian) for x, y in points)
 
 
+def linestring_wkb(points, big_endian=True):
+    """LineString of (x, y) tuples (JTS WKBWriter layout)."""
+    bo = ">" if big_endian else "<"
+    head = struct.pack(bo + "BII", 0 if big_endian else 1, WKB_LINESTRING, len(points))
+    return head + b"".join(struct.pack(bo + "dd", x, y) for x, y in points)
+
+
+def multilinestring_wkb(lines, big_endian=True):
+    """MultiLineString of lists of (x, y) tuples (JTS WKBWriter layout)."""
+    bo = ">" if big_endian else "<"
+    head = struct.pack(bo + "BII", 0 if big_endian else 1, WKB_MULTILINESTRING, len(lines))
+    return head + b"".join(linestring_wkb(ln, big_endian) for ln in lines)
+
+
 def _read_geom(buf, pos):
     le = buf[pos] == 1
     bo = "<" if le else ">"
@@ -63,6 +80,21 @@ def _read_geom(buf, pos):
     if t == WKB_POINT:
         vals = struct.unpack_from(bo + "d" * dims, buf, pos)
         return ("point", (vals[0], vals[1])), pos + 8 * dims
+    if t == WKB_LINESTRING:
+        (npts,) = struct.unpack_from(bo + "I", buf, pos)
+        pos += 4
+        vals = struct.unpack_from(bo + "d" * (dims * npts), buf, pos)
+        return ("linestring", [[(vals[dims * k], vals[dims * k + 1]) for k in range(npts)]]), pos + 8 * dims * npts
+    if t == WKB_MULTILINESTRING:
+        (nl,) = struct.unpack_from(bo + "I", buf, pos)
+        pos += 4
+        lines = []
+        for _ in range(nl):
+            (kind, g), pos = _read_geom(buf, pos)
+            if kind != "linestring":
+                raise ValueError("MultiLineString member is not a LineString")
+            lines.extend(g)
+        return ("linestring", lines), pos
     if t == WKB_POLYGON:
         (nr,) = struct.unpack_from(bo + "I", buf, pos)
         pos += 4
@@ -98,7 +130,8 @@ def _read_geom(buf, pos):
 
 
 def read_wkb(buf):
-    """Returns ('point', (x, y)), ('multipoint', [(x, y), ...]) or ('polygon', parts)."""
+    """Returns ('point', (x, y)), ('multipoint', [(x, y), ...]), ('polygon', parts) or
+    ('linestring', lines): the component lines of a LineString (one) or MultiLineString."""
     g, _ = _read_geom(bytes(buf), 0)
     return g
 
@@ -118,13 +151,16 @@ def _parse_ring_list(txt):
 
 
 def read_wkt(text):
-    """Minimal WKT reader for POINT / MULTIPOINT / POLYGON / MULTIPOLYGON (JTS WKTReader subset)."""
+    """Minimal WKT reader for POINT / MULTIPOINT / POLYGON / MULTIPOLYGON / LINESTRING /
+    MULTILINESTRING (JTS WKTReader subset)."""
     t = text.strip()
     head = t.split("(", 1)[0].strip().upper()
     if head.endswith("EMPTY") or t.upper().endswith("EMPTY"):
         kind = head.split()[0]
         if kind == "MULTIPOINT":
             return ("multipoint", [])
+        if kind in ("LINESTRING", "MULTILINESTRING"):
+            return ("linestring", [])
         return ("point", None) if kind == "POINT" else ("polygon", [])
     if head == "MULTIPOINT":
         # both of JTS's forms: MULTIPOINT ((1 2), (3 4)) and MULTIPOINT (1 2, 3 4)
@@ -138,6 +174,12 @@ def read_wkt(text):
     if head == "POINT":
         nums = re.findall(_NUM, t)
         return ("point", (float(nums[0]), float(nums[1])))
+    if head == "LINESTRING":
+        return ("linestring", _parse_ring_list(t))
+    if head == "MULTILINESTRING":
+        inner = t[t.index("(") + 1:t.rindex(")")]
+        return ("linestring", [[] if m.group(1) is None else _parse_ring_list(m.group(0))[0]
+                               for m in re.finditer(r"\(([^()]*)\)|EMPTY", inner, re.I)])
     if head == "POLYGON":
         return ("polygon", [_parse_ring_list(t)])
     if head == "MULTIPOLYGON":
