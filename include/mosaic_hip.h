@@ -434,6 +434,62 @@ int mosaic_intersects_aggregate(mosaic_ctx* ctx, const mosaic_chips* left, const
                                 int32_t* out_left_key, int32_t* out_right_key, uint8_t* out_flag, int64_t cap,
                                 int64_t* n_out);
 
+/* ---- st_intersects_aggregate over the join of line chips with polygon chips ---- */
+/* The reason lines are tessellated: "which trips cross which zones" is the equi-join of two
+ * grid_tessellateexplode outputs on index_id, grouped by (line row, polygon row) and folded with
+ * st_intersects_aggregate.  getChips sends LINESTRING / MULTILINESTRING to lineFill
+ * (core/Mosaic.scala:21-35) and ST_IntersectsAggregate.update decodes whatever WKB a chip holds
+ * (expressions/geometry/ST_IntersectsAggregate.scala:28-39).
+ * Semantics: one group per (line key, polygon key) whose chip sets share a cell id (the group exists
+ * even when its flag is false); flag = OR over the group's chip pairs of l.is_core || p.is_core ||
+ * intersects(l.wkb, p.wkb).  lineFill's chips are never core, but the column is honoured literally.
+ * intersects is JTS Geometry.intersects (the closed point sets share a point), restated in
+ * mosaic_amd/csrc/line_isect.h on exact predicates: (1) a side without a coordinate: false; (2) the
+ * chips' envelopes do not meet: false; (3) a segment of a piece meets a ring segment of the polygon
+ * chip, holes included: true; (4) the first vertex of some piece -- every POINT / MULTIPOINT item is a
+ * piece -- is inside or on the boundary of some polygon part: true; (5) false.  Host and GPU answers
+ * are equal, not close.
+ * A line chip set is the chip columns of mosaic_tessellate_lines: WKB types 1 POINT (NaN ordinates:
+ * an empty chip), 4 MULTIPOINT, 2 LINESTRING (no points: an empty chip), 5 MULTILINESTRING, either byte
+ * order, ISO Z/M and EWKB flags; a zero-length row is an empty chip.
+ * Errors: MOSAIC_E_WKB naming the row for any other type, a truncated buffer, a member of another type
+ * inside a multi-geometry, a LineString of exactly one point; MOSAIC_E_NAN for a NaN inside a line;
+ * MOSAIC_E_ARG for a negative key, decreasing offsets, or tables of different grid / resolution;
+ * MOSAIC_E_CAPACITY at 2^31 chips or 2^32 - 1 vertices, and -- with *n_out = the required size -- when
+ * more than `cap` groups exist.  Groups are written sorted by (line key, polygon key). */
+typedef struct mosaic_line_chips mosaic_line_chips;
+/* The device-resident line chip table (immutable after creation).  wkb_offsets: n_chips + 1 offsets
+ * into wkb, int32 when offsets32 != 0, else int64 (Arrow binary / large_binary). */
+int mosaic_line_chips_create(mosaic_ctx* ctx, int grid, int res, int64_t n_chips, const uint8_t* is_core,
+                             const int64_t* index_id, const int32_t* key, const void* wkb_offsets, int offsets32,
+                             const uint8_t* wkb, mosaic_line_chips** out);
+/* out4 = chips, pieces (a piece of one vertex is a point), vertices, device bytes. */
+int mosaic_line_chips_info(const mosaic_line_chips* lines, int64_t* out4);
+int mosaic_line_chips_destroy(mosaic_line_chips* lines);
+/* The join on the GPU: k_lj_probe (one lane per line chip; probes the polygon table's cell hash, finds
+ * or inserts every chip pair's group, lists the pairs that need the geometry test) and k_lj_test (one
+ * team of lanes per listed pair); k_lj_groups then packs the groups for the copy back.  The output
+ * protocol is mosaic_intersects_aggregate's. */
+int mosaic_line_intersects_aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chips* polygons,
+                                     int32_t* out_line_key, int32_t* out_polygon_key, uint8_t* out_flag, int64_t cap,
+                                     int64_t* n_out);
+/* The calling thread's last mosaic_line_intersects_aggregate: out = line chips whose cell the polygon
+ * table holds, chip pairs, pairs geometry-tested, groups; ms = device time (HIP events) of k_lj_probe
+ * (both passes) and of k_lj_test. */
+int mosaic_line_join_last(int64_t out[4], double ms[2]);
+/* Lanes per pair of k_lj_test for the process's later calls: 64 (one wave per pair) or 16 (four pairs
+ * per wave); another value changes nothing.  Returns the previous width.  The answers do not depend on
+ * it; it exists to measure the two forms. */
+int mosaic_line_join_team(int lanes);
+/* The same join on the host, on at most 16 threads: no context, no GPU.  Polygon chips are decoded as
+ * mosaic_chip_table_create decodes them (Polygon / MultiPolygon), line chips as above; offsets are
+ * int64. */
+int mosaic_line_intersects_aggregate_host(int grid, int res, int64_t n_l, const uint8_t* l_core, const int64_t* l_cell,
+                                          const int32_t* l_key, const int64_t* l_off, const uint8_t* l_wkb, int64_t n_p,
+                                          const uint8_t* p_core, const int64_t* p_cell, const int32_t* p_key,
+                                          const int64_t* p_off, const uint8_t* p_wkb, int32_t* out_line_key,
+                                          int32_t* out_polygon_key, uint8_t* out_flag, int64_t cap, int64_t* n_out);
+
 /* ---- st_intersection_aggregate over the chip join of two chip tables ---- */
 /* For every (left polygon_key, right polygon_key) pair whose chip sets share a cell id: the union
  * ST_IntersectionAggregate.update / merge (expressions/geometry/ST_IntersectionAggregate.scala:40-72)

@@ -4,9 +4,9 @@ Product path: libmosaic_hip.so (mosaic_amd/csrc, HIP for gfx950) behind the C AB
 include/mosaic_hip.h; this package is the host-side mirror of the reference's function surface.
 """
 from ._native import IllegalStateException, MosaicError, NativeUnavailable  # noqa: F401
-from .context import (BNGIndexSystem, ChipTable, GeometryTable, H3IndexSystem, MosaicContext,  # noqa: F401
-                      RowPathRequired)
+from .context import (BNGIndexSystem, ChipTable, GeometryTable, H3IndexSystem, LineChipTable, MosaicContext,  # noqa: F401
+                      RowPathRequired, line_intersects_aggregate_host)
 from .knn import CellIndex, SpatialKNN  # noqa: F401
 
-__all__ = ["MosaicContext", "ChipTable", "GeometryTable", "CellIndex", "SpatialKNN", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
+__all__ = ["MosaicContext", "ChipTable", "LineChipTable", "line_intersects_aggregate_host", "GeometryTable", "CellIndex", "SpatialKNN", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
            "MosaicError", "NativeUnavailable"]

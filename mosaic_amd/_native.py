@@ -49,6 +49,9 @@ EXPORTS = [
     "mosaic_cell_index_create", "mosaic_cell_index_info", "mosaic_cell_index_destroy", "mosaic_ring_neighbours",
     "mosaic_neighbours_info", "mosaic_neighbours_export", "mosaic_neighbours_destroy", "mosaic_ring_neighbours_last_ms",
     "mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last",
+    "mosaic_line_chips_create", "mosaic_line_chips_info", "mosaic_line_chips_destroy",
+    "mosaic_line_intersects_aggregate", "mosaic_line_join_last", "mosaic_line_join_team",
+    "mosaic_line_intersects_aggregate_host",
 ]
 
 GEOM_WKB = 0
@@ -143,6 +146,14 @@ def lib():
         "mosaic_tessellate_lines": ([i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
         "mosaic_tessellate_lines_gpu": ([vp, i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
         "mosaic_tess_lines_last": ([vp, vp], i32),
+        "mosaic_line_chips_create": ([vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_line_chips_info": ([vp, vp], i32),
+        "mosaic_line_chips_destroy": ([vp], i32),
+        "mosaic_line_intersects_aggregate": ([vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),
+        "mosaic_line_join_last": ([vp, vp], i32),
+        "mosaic_line_join_team": ([i32], i32),
+        "mosaic_line_intersects_aggregate_host": ([i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                                   ctypes.POINTER(i64)], i32),
         "mosaic_tess_last_classify_ms": ([vp], ctypes.c_double),
         "mosaic_tess_counters": ([ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_point_to_cell_exact": ([vp, i32, vp, vp, i64, vp], i32),

@@ -211,39 +211,48 @@ def _points_xy(points):
     return None
 
 
+def _chip_columns(ctx, is_core, index_id, wkb_list, key):
+    """Chip columns as the contiguous arrays the library reads: (is_core uint8, index_id int64,
+    key int32, wkb offsets int32 / int64, wkb data uint8).  wkb_list: an Arrow (offsets, data) pair or
+    a list of bytes / None."""
+    is_core = np.ascontiguousarray(is_core, dtype=np.uint8)
+    strings = not _is_arrow_utf8(index_id) and len(index_id) and isinstance(index_id[0], str)
+    if ctx.index_system.cell_id_type == "string" and (_is_arrow_utf8(index_id) or strings):
+        # StringType ids (the BNG default, BNGIndexSystem.scala:28): parsed on the GPU
+        index_id = ctx.bng_parse_column(index_id)
+    elif strings:
+        # string ids of a LongType index system (H3 hex strings, H3IndexSystem.parse)
+        index_id = [ctx.index_system.parse(v) for v in index_id]
+    elif _is_arrow_utf8(index_id):
+        raise ValueError(f"an Arrow utf8 id column needs a StringType index system, not {ctx.index_system.name}")
+    index_id = np.ascontiguousarray(index_id, dtype=np.int64)
+    key = np.ascontiguousarray(key, dtype=np.int32)
+    if isinstance(wkb_list, tuple) and len(wkb_list) == 2:
+        # Arrow binary (int32 offsets) or large_binary (int64)
+        offsets = np.ascontiguousarray(wkb_list[0])
+        if offsets.dtype != np.int32:
+            offsets = offsets.astype(np.int64, copy=False)
+        data = np.ascontiguousarray(wkb_list[1], dtype=np.uint8)
+    else:
+        lens = np.array([0 if w is None else len(w) for w in wkb_list], dtype=np.int64)
+        offsets = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        data = np.frombuffer(b"".join(b"" if w is None else bytes(w) for w in wkb_list), dtype=np.uint8)
+        data = np.ascontiguousarray(data) if len(data) else np.zeros(1, np.uint8)
+    n = len(index_id)
+    if not (len(is_core) == n == len(key) == len(offsets) - 1):
+        raise ValueError("chip columns have different lengths")
+    return is_core, index_id, key, offsets, data
+
+
 class ChipTable:
     """Device-resident build side of the chip join: rows of ChipType(is_core, index_id, wkb) plus the
     key of the polygon each chip belongs to (core/types/ChipType.scala:17-28)."""
 
     def __init__(self, ctx, is_core, index_id, wkb_list, polygon_key, n_polygons=None):
         self.ctx = ctx
-        is_core = np.ascontiguousarray(is_core, dtype=np.uint8)
-        strings = not _is_arrow_utf8(index_id) and len(index_id) and isinstance(index_id[0], str)
-        if ctx.index_system.cell_id_type == "string" and (_is_arrow_utf8(index_id) or strings):
-            # StringType ids (the BNG default, BNGIndexSystem.scala:28): parsed on the GPU
-            index_id = ctx.bng_parse_column(index_id)
-        elif strings:
-            # string ids of a LongType index system (H3 hex strings, H3IndexSystem.parse)
-            index_id = [ctx.index_system.parse(v) for v in index_id]
-        elif _is_arrow_utf8(index_id):
-            raise ValueError(f"an Arrow utf8 id column needs a StringType index system, not {ctx.index_system.name}")
-        index_id = np.ascontiguousarray(index_id, dtype=np.int64)
-        polygon_key = np.ascontiguousarray(polygon_key, dtype=np.int32)
-        if isinstance(wkb_list, tuple) and len(wkb_list) == 2:
-            # Arrow binary (int32 offsets) or large_binary (int64)
-            offsets = np.ascontiguousarray(wkb_list[0])
-            if offsets.dtype != np.int32:
-                offsets = offsets.astype(np.int64, copy=False)
-            data = np.ascontiguousarray(wkb_list[1], dtype=np.uint8)
-        else:
-            lens = np.array([0 if w is None else len(w) for w in wkb_list], dtype=np.int64)
-            offsets = np.zeros(len(lens) + 1, np.int64)
-            np.cumsum(lens, out=offsets[1:])
-            data = np.frombuffer(b"".join(b"" if w is None else bytes(w) for w in wkb_list), dtype=np.uint8)
-            data = np.ascontiguousarray(data) if len(data) else np.zeros(1, np.uint8)
+        is_core, index_id, polygon_key, offsets, data = _chip_columns(ctx, is_core, index_id, wkb_list, polygon_key)
         n = len(index_id)
-        if not (len(is_core) == n == len(polygon_key) == len(offsets) - 1):
-            raise ValueError("chip columns have different lengths")
         if n_polygons is None:
             n_polygons = int(polygon_key.max()) + 1 if n else 0
         self.n_polygons = int(n_polygons)
@@ -323,6 +332,73 @@ class ChipTable:
             self.close()
         except Exception:
             pass
+
+
+class LineChipTable:
+    """Device-resident line chips (grid_tessellateexplode over a LineSet, Mosaic.lineFill): rows of
+    ChipType(is_core, index_id, wkb) holding LINESTRING / MULTILINESTRING pieces or POINT / MULTIPOINT
+    contacts, plus the key of the line each chip belongs to.  The line side of
+    MosaicContext.st_intersects_aggregate.  wkb: an Arrow (offsets, data) pair or a list of bytes / None."""
+
+    def __init__(self, ctx, is_core, index_id, wkb, key, resolution):
+        self.ctx = ctx
+        is_core, index_id, key, offsets, data = _chip_columns(ctx, is_core, index_id, wkb, key)
+        self.n_chips = len(index_id)
+        h = ctypes.c_void_p()
+        N.check(N.lib().mosaic_line_chips_create(
+            ctx.handle, ctx.index_system.grid, ctx.index_system.get_resolution(resolution), self.n_chips,
+            N.ptr(is_core), N.ptr(index_id), N.ptr(key), N.ptr(offsets), 1 if offsets.dtype == np.int32 else 0,
+            N.ptr(data), ctypes.byref(h)))
+        self.handle = h
+
+    def info(self):
+        out = np.zeros(4, np.int64)
+        N.check(N.lib().mosaic_line_chips_info(self.handle, N.ptr(out)))
+        return dict(zip(["n_chips", "n_pieces", "n_vertices", "device_bytes"], (int(v) for v in out)))
+
+    def close(self):
+        if self.handle:
+            N.lib().mosaic_line_chips_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def line_intersects_aggregate_host(index_system, line_chips, polygon_chips, resolution):
+    """st_intersects_aggregate over the join of line chips with polygon chips on the host
+    (mosaic_line_intersects_aggregate_host: no context, no GPU): the two chip dicts `tessellate`
+    returns -> (line_key int32, polygon_key int32, flag bool), sorted by (line key, polygon key)."""
+    if isinstance(index_system, str):
+        index_system = INDEX_SYSTEMS[index_system]()
+    res = index_system.get_resolution(resolution)
+
+    def cols(c):
+        off = np.ascontiguousarray(c["wkb"][0], dtype=np.int64)
+        data = np.ascontiguousarray(c["wkb"][1], dtype=np.uint8)
+        return (len(c["index_id"]), np.ascontiguousarray(c["is_core"], dtype=np.uint8),
+                np.ascontiguousarray(c["index_id"], dtype=np.int64), np.ascontiguousarray(c["polygon_key"], dtype=np.int32),
+                off if len(off) else np.zeros(1, np.int64), data if len(data) else np.zeros(1, np.uint8))
+
+    L, P = cols(line_chips), cols(polygon_chips)
+    cap = 1024
+    while True:
+        lk = np.empty(cap, np.int32)
+        pk = np.empty(cap, np.int32)
+        fl = np.empty(cap, np.uint8)
+        n_out = ctypes.c_int64(0)
+        rc = N.lib().mosaic_line_intersects_aggregate_host(
+            index_system.grid, res, L[0], *[N.ptr(a) for a in L[1:]], P[0], *[N.ptr(a) for a in P[1:]],
+            N.ptr(lk), N.ptr(pk), N.ptr(fl), cap, ctypes.byref(n_out))
+        if rc == N.MOSAIC_E_CAPACITY and n_out.value > cap:
+            cap = int(n_out.value)
+            continue
+        N.check(rc)
+        k = int(n_out.value)
+        return lk[:k], pk[:k], fl[:k].astype(bool)
 
 
 _WKB_ROW_PATH = b"\x00\x00\x00\x00\x02\x00\x00\x00\x00"  # LINESTRING EMPTY: stands for a row the engine does not serve
@@ -818,6 +894,10 @@ class MosaicContext:
         self.resolution_of_table = self.index_system.get_resolution(resolution)
         return ChipTable(self, is_core, index_id, wkb_list, polygon_key, n_polygons)
 
+    def line_chip_table(self, is_core, index_id, wkb_list, key, resolution):
+        """The line side of st_intersects_aggregate: rows of grid_tessellateexplode over a LineSet."""
+        return LineChipTable(self, is_core, index_id, wkb_list, key, resolution)
+
     def chip_table_arrays(self, chip_offsets, is_core, index_id, wkb_list, resolution):
         """Build side from grid_tessellate chip arrays, one array per polygon row (the array form of
         PointInPolygonJoin, sql/join/PointInPolygonJoin.scala:39-66); see ChipTable.from_arrays."""
@@ -1101,15 +1181,27 @@ class MosaicContext:
         .agg(st_intersects_aggregate(left_index, right_index)) over two chip tables
         (ST_IntersectsAggregate.scala:28-39, ST_IntersectsBehaviors.scala:34-47): arrays
         (left_key int32, right_key int32, flag bool) sorted by (left_key, right_key), one row per key
-        pair that shares a cell id."""
+        pair that shares a cell id.
+
+        One side may be a LineChipTable (the chips of grid_tessellateexplode over a LineSet): "which
+        trips cross which zones" (mosaic_line_intersects_aggregate).  With the line table on the right
+        the columns come back swapped and sorted by (left key, right key) all the same.  Two line
+        tables raise ValueError."""
+        lines = (isinstance(left, LineChipTable), isinstance(right, LineChipTable))
+        if all(lines):
+            raise ValueError("st_intersects_aggregate: a line x line join is not served")
+        if lines[1]:
+            rk, lk, fl = self.st_intersects_aggregate(right, left)
+            order = np.lexsort((rk, lk))
+            return lk[order], rk[order], fl[order]
+        fn = N.lib().mosaic_line_intersects_aggregate if lines[0] else N.lib().mosaic_intersects_aggregate
         cap = 1024
         while True:
             lk = np.empty(cap, np.int32)
             rk = np.empty(cap, np.int32)
             fl = np.empty(cap, np.uint8)
             n_out = ctypes.c_int64(0)
-            rc = N.lib().mosaic_intersects_aggregate(self.handle, left.handle, right.handle, N.ptr(lk), N.ptr(rk),
-                                                     N.ptr(fl), cap, ctypes.byref(n_out))
+            rc = fn(self.handle, left.handle, right.handle, N.ptr(lk), N.ptr(rk), N.ptr(fl), cap, ctypes.byref(n_out))
             if rc == N.MOSAIC_E_CAPACITY and n_out.value > cap:
                 cap = int(n_out.value)
                 continue

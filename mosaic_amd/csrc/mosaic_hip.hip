@@ -33,6 +33,7 @@
 
 #include "../../include/mosaic_hip.h"
 #include "bng_device.h"
+#include "chips_view.h"
 #include "geom_build.h"
 #include "h3_device.h"
 #include "h3_geom.h"
@@ -2428,6 +2429,20 @@ int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int
     *tile = ctx->opt.dist_tile;
     *small_work = ctx->opt.dist_small_work;
     *prune = ctx->opt.dist_prune;
+    return MOSAIC_OK;
+}
+
+// what k_isect_agg reads from a chip table, for line_join.hip
+int mosaic_chips_join_view(const mosaic_chips* chips, ChipsJoinView* out) {
+    if (!chips || !out) return fail(MOSAIC_E_ARG, "null chip table");
+    out->table = (const HashEntry*)chips->table.p;
+    out->capacity = chips->capacity;
+    out->meta = (const uint32_t*)chips->meta.p;
+    out->store = chips->store.view();
+    out->grid = chips->grid;
+    out->res = chips->res;
+    out->device = chips->device;
+    out->n_chips = chips->n_chips;
     return MOSAIC_OK;
 }
 
