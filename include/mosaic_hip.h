@@ -624,16 +624,33 @@ double mosaic_geometry_kring_last_ms(void);
  * expressions/geometry/ST_Distance.scala:34-36 -> JTS Geometry.distance; step 3 of the KNN iteration,
  * models/knn/GridRingNeighbours.scala:153-156) ---- */
 /* A device-resident geometry column: immutable after creation, usable from any thread (like a chip
- * table), freed with mosaic_geoms_destroy.  Rows are Point, MultiPoint, Polygon or MultiPolygon.
+ * table), freed with mosaic_geoms_destroy.  Rows are Point, MultiPoint, LineString, MultiLineString,
+ * Polygon or MultiPolygon; line rows are served by the columns that ask for them (below).
  * _wkb: row i is wkb[offsets[i] .. offsets[i + 1]) (either byte order, ISO Z/M and EWKB variants);
  *   valid[i] == 0 is a null row (MOSAIC_ROW_NULL); LineString, MultiLineString, GeometryCollection,
  *   POINT EMPTY and undecodable rows are MOSAIC_ROW_PATH (the convention of
  *   mosaic_point_geom_to_cell), not an error of the call.
+ * _wkb_ex: _wkb with flags.  MOSAIC_GEOMS_LINES: LineString and MultiLineString rows are decoded
+ *   (through the same reader) into line parts -- each component line an open run of n >= 2 vertices
+ *   with n - 1 segments, never closed and never a container -- and are MOSAIC_ROW_OK; LINESTRING
+ *   EMPTY / MULTILINESTRING EMPTY are MOSAIC_ROW_OK rows at distance 0.0 from everything, an empty
+ *   member adds nothing, a component of exactly one vertex makes the row MOSAIC_ROW_PATH.  flags 0 is
+ *   _wkb: a column built without the flag keeps line rows as MOSAIC_ROW_PATH, on purpose, so callers
+ *   that send such rows to the row path see no change.  An unknown flag: MOSAIC_E_ARG.
  * _arrays: polygonal geometries in the flat-ring layout of mosaic_polyfill (host pointers).
+ * _lines: line geometries in the layout of mosaic_tessellate_lines (host pointers): geometry g is the
+ *   component lines [geom_lines[g], geom_lines[g + 1]), line l the vertices [line_offsets[l],
+ *   line_offsets[l + 1]) of xy (interleaved).  Rows as under MOSAIC_GEOMS_LINES; inconsistent offsets:
+ *   MOSAIC_E_ARG.
  * _points: row i is POINT (x[i] y[i]); host or device pointers; a NaN coordinate is MOSAIC_ROW_PATH. */
 typedef struct mosaic_geoms mosaic_geoms;
+#define MOSAIC_GEOMS_LINES 1u
 int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb,
                             const uint8_t* valid /*nullable*/, mosaic_geoms** out);
+int mosaic_geoms_create_wkb_ex(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb,
+                               const uint8_t* valid /*nullable*/, uint32_t flags, mosaic_geoms** out);
+int mosaic_geoms_create_lines(mosaic_ctx* ctx, int64_t n, const int64_t* geom_lines, const int64_t* line_offsets,
+                              const double* xy, mosaic_geoms** out);
 int mosaic_geoms_create_arrays(mosaic_ctx* ctx, int64_t n, const int64_t* geom_parts, const int64_t* part_rings,
                                const int64_t* ring_offsets, const double* xy, mosaic_geoms** out);
 int mosaic_geoms_create_points(mosaic_ctx* ctx, const double* x, const double* y, int64_t n, mosaic_geoms** out);
@@ -642,7 +659,8 @@ int mosaic_geoms_destroy(mosaic_geoms* geoms);
 /* out[i] = st_distance(left[left_row[i]], right[right_row[i]]); left_row == right_row == NULL: row i
  * with row i (n_pairs rows of both columns).  The value is that of the sequential definition in
  * mosaic_amd/csrc/st_distance.h, bit for bit: 0.0 when either geometry is empty or one holds a
- * component of the other, otherwise the smallest JTS segment / point distance over all facet pairs.
+ * component of the other (only polygons hold; a line never does, closed or not), otherwise the
+ * smallest JTS segment / point distance over all facet pairs.
  * status[i] (nullable): MOSAIC_ROW_OK; MOSAIC_ROW_NULL (either side null, out NaN); MOSAIC_ROW_PATH
  * (either side a row-path row, out NaN).  A row index out of range: MOSAIC_E_ARG, nothing written.
  * out / status / the row arrays: host or device pointers.  Options: "dist_tile" (segments per LDS

@@ -51,7 +51,7 @@ EXPORTS = [
     "mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last",
     "mosaic_line_chips_create", "mosaic_line_chips_info", "mosaic_line_chips_destroy",
     "mosaic_line_intersects_aggregate", "mosaic_line_join_last", "mosaic_line_join_team",
-    "mosaic_line_intersects_aggregate_host",
+    "mosaic_line_intersects_aggregate_host", "mosaic_geoms_create_wkb_ex", "mosaic_geoms_create_lines",
 ]
 
 GEOM_WKB = 0
@@ -61,6 +61,7 @@ GEOM_OFFSETS32 = 0x100
 ROW_NULL = 0
 ROW_OK = 1
 ROW_PATH = 2
+GEOMS_LINES = 1  # mosaic_geoms_create_wkb_ex: decode LineString / MultiLineString rows
 
 
 class NativeUnavailable(RuntimeError):
@@ -173,6 +174,8 @@ def lib():
         "mosaic_cell_lists_export_dist": ([vp, vp], i32),
         "mosaic_geometry_kring_last_ms": ([], ctypes.c_double),
         "mosaic_geoms_create_wkb": ([vp, i64, vp, vp, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_geoms_create_wkb_ex": ([vp, i64, vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(vp)], i32),
+        "mosaic_geoms_create_lines": ([vp, i64, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_geoms_create_arrays": ([vp, i64, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_geoms_create_points": ([vp, vp, vp, i64, ctypes.POINTER(vp)], i32),
         "mosaic_geoms_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

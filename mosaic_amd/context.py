@@ -404,34 +404,53 @@ def line_intersects_aggregate_host(index_system, line_chips, polygon_chips, reso
 _WKB_ROW_PATH = b"\x00\x00\x00\x00\x02\x00\x00\x00\x00"  # LINESTRING EMPTY: stands for a row the engine does not serve
 
 
-def _wkt_row_wkb(text):
-    """A WKT row as the WKB the geometry column decodes; what wkb.read_wkt does not read (line
-    geometries, collections, malformed text) becomes a row for the row path."""
+_WKB_ROW_PATH_LINES = b"\x00\x00\x00\x00\x07\x00\x00\x00\x00"  # GEOMETRYCOLLECTION EMPTY: the same, in a column that serves lines
+
+
+def _wkt_row_wkb(text, lines=False):
+    """A WKT row as the WKB the geometry column decodes; what wkb.read_wkt does not read
+    (collections, malformed text; line geometries unless ``lines``) becomes a row for the row path.
+    With ``lines`` LINESTRING / MULTILINESTRING text is converted too, and the row-path marker is
+    GEOMETRYCOLLECTION EMPTY: LINESTRING EMPTY is a served row there."""
+    row_path = _WKB_ROW_PATH_LINES if lines else _WKB_ROW_PATH
+    kinds = ("POINT", "MULTIPOINT", "POLYGON", "MULTIPOLYGON") + (("LINESTRING", "MULTILINESTRING") if lines else ())
     head = text.split("(", 1)[0].split()
-    if not head or head[0].upper() not in ("POINT", "MULTIPOINT", "POLYGON", "MULTIPOLYGON"):
-        return _WKB_ROW_PATH
+    if not head or head[0].upper() not in kinds:
+        return row_path
     try:
         kind, g = W.read_wkt(text)
     except (ValueError, IndexError):
-        return _WKB_ROW_PATH
+        return row_path
     if kind == "point":
         return W.point_wkb(*(g if g is not None else (float("nan"), float("nan"))))
     if kind == "multipoint":
         return W.multipoint_wkb(g)
+    if kind == "linestring":
+        if not g and not text.rstrip().upper().endswith("EMPTY"):  # no component was read from text that is not EMPTY
+            return row_path
+        return W.multilinestring_wkb(g) if len(g) > 1 else W.linestring_wkb(g[0] if g else [])
     return W.geometry_wkb(g) if len(g) != 1 else W.polygon_wkb(g[0])
 
 
 class GeometryTable:
-    """A device-resident geometry column (mosaic_geoms): Point, MultiPoint, Polygon and MultiPolygon
-    rows in the flat ring layout, immutable after creation and usable from any thread, for
-    ``MosaicContext.st_distance``.  The KNN iteration evaluates distances against the same candidate
+    """A device-resident geometry column (mosaic_geoms): Point, MultiPoint, LineString,
+    MultiLineString, Polygon and MultiPolygon rows in the flat ring layout, immutable after creation
+    and usable from any thread, for ``MosaicContext.st_distance``.  Line rows are served by a table
+    built from a LineSet or with ``lines=True``; in a table of WKB / WKT rows built without it they
+    stay rows for the row path.  The KNN iteration evaluates distances against the same candidate
     column on every round (models/knn/GridRingNeighbours.scala:76-99), so the column outlives a call.
     Built by ``MosaicContext.geometry_table``; ``close()`` frees the device memory."""
 
-    def __init__(self, ctx, geoms):
+    def __init__(self, ctx, geoms, lines=False):
         self.ctx = ctx
         h = ctypes.c_void_p()
         lib = N.lib()
+        if hasattr(geoms, "geom_lines"):  # a LineSet
+            N.check(lib.mosaic_geoms_create_lines(ctx.handle, len(geoms), N.ptr(geoms.geom_lines), N.ptr(geoms.line_offsets),
+                                                  N.ptr(geoms.xy), ctypes.byref(h)))
+            self.handle = h
+            self.n_geoms = self.info()["n_geoms"]
+            return
         rows_given = isinstance(geoms, (list, tuple)) and any(g is None or isinstance(g, (str, bytes, bytearray, memoryview))
                                                             for g in geoms)
         xy = None if hasattr(geoms, "geom_parts") or rows_given else _points_xy(geoms)
@@ -447,10 +466,14 @@ class GeometryTable:
         else:
             if isinstance(geoms, (str, bytes, bytearray)):
                 geoms = [geoms]
-            rows = [_wkt_row_wkb(g) if isinstance(g, str) else g for g in geoms]
+            rows = [_wkt_row_wkb(g, lines) if isinstance(g, str) else g for g in geoms]
             _, offsets, data, valid = geometry_column(rows)
-            N.check(lib.mosaic_geoms_create_wkb(ctx.handle, len(rows), N.ptr(offsets), N.ptr(data), N.ptr(valid),
-                                                ctypes.byref(h)))
+            if lines:
+                N.check(lib.mosaic_geoms_create_wkb_ex(ctx.handle, len(rows), N.ptr(offsets), N.ptr(data), N.ptr(valid),
+                                                       N.GEOMS_LINES, ctypes.byref(h)))
+            else:
+                N.check(lib.mosaic_geoms_create_wkb(ctx.handle, len(rows), N.ptr(offsets), N.ptr(data), N.ptr(valid),
+                                                    ctypes.byref(h)))
         self.handle = h
         info = self.info()
         self.n_geoms = info["n_geoms"]
@@ -784,25 +807,32 @@ class MosaicContext:
         return out.astype(bool)
 
     # ---- st_distance ----
-    def geometry_table(self, geoms):
+    def geometry_table(self, geoms, lines=False):
         """A ``GeometryTable``: ``geoms`` as a device-resident geometry column.  Accepts a PolygonSet;
-        a sequence of WKB (bytes) or WKT (str) rows of POINT / MULTIPOINT / POLYGON / MULTIPOLYGON,
-        None = null (one row may be given bare); or points as an ``(x, y)`` pair or an ``[n, 2]``
-        array or tensor, on the host or the device.  Line geometries, collections, POINT EMPTY and
-        undecodable rows are kept as rows for the reference's row path."""
-        return GeometryTable(self, geoms)
+        a LineSet (LineString / MultiLineString rows; a component of one vertex makes its row a row
+        for the row path); a sequence of WKB (bytes) or WKT (str) rows of POINT / MULTIPOINT /
+        POLYGON / MULTIPOLYGON, None = null (one row may be given bare); or points as an ``(x, y)``
+        pair or an ``[n, 2]`` array or tensor, on the host or the device.  Collections, POINT EMPTY
+        and undecodable rows are kept as rows for the reference's row path.  So are LINESTRING /
+        MULTILINESTRING rows among WKB / WKT rows, unless ``lines=True``: then they are served like
+        the rows of a LineSet (LINESTRING EMPTY is a served row at distance 0.0).  ``lines`` changes
+        nothing for a PolygonSet, a LineSet or points."""
+        return GeometryTable(self, geoms, lines)
 
     def st_distance(self, left, right, pairs=None, return_status=False):
         """st_distance(left, right) (functions/MosaicContext.scala:146 ST_Distance ->
         expressions/geometry/ST_Distance.scala:34-36 -> core/geometry/MosaicGeometryJTS.distance ->
         JTS 1.19 Geometry.distance / DistanceOp.distance; docs/source/api/spatial-functions.rst:416-471),
         and step 3 of the KNN iteration (models/knn/GridRingNeighbours.scala:153-156), on this
-        context's GPU (mosaic_st_distance): 0.0 when either geometry is empty or one contains a
-        component of the other, otherwise the smallest JTS segment / point distance over all pairs of
-        facets -- the bits of the sequential definition in mosaic_amd/csrc/st_distance.h.
+        context's GPU (mosaic_st_distance): 0.0 when either geometry is empty or a polygon of one
+        contains a component of the other (a line contains nothing, closed or not), otherwise the
+        smallest JTS segment / point distance over all pairs of facets -- the bits of the sequential
+        definition in mosaic_amd/csrc/st_distance.h.  Point, MultiPoint, LineString, MultiLineString,
+        Polygon and MultiPolygon rows are served on either side.
 
-        ``left`` / ``right``: ``GeometryTable``s, or anything ``geometry_table`` accepts (the table
-        is then built and closed inside the call).  ``pairs=None`` is row-wise: the lengths match, or
+        ``left`` / ``right``: ``GeometryTable``s, or anything ``geometry_table`` accepts, a LineSet
+        included (the table is then built and closed inside the call; WKB / WKT line rows need a
+        table built with ``lines=True``).  ``pairs=None`` is row-wise: the lengths match, or
         one side is a single geometry that every row of the other is measured against (as in
         ``st_contains``).  ``pairs=(left_idx, right_idx)`` evaluates exactly those (left row, right
         row) pairs; the index arrays may live on the device.  Returns a float64 array with NaN on

@@ -1,10 +1,18 @@
 // Host-side builder of a geometry column (mosaic_geoms, st_distance.hip) in the flat ring layout of
-// pip_device.h, for the geometry types st_distance serves: Point, MultiPoint, Polygon, MultiPolygon.
-// A point is a part of kind kPartPoint with one ring of one vertex (st_distance.h).  WKB rows are
-// decoded with GeomBuilder's reader (either byte order, ISO Z/M and EWKB flag variants); what the
-// chip tables and mosaic_st_contains accept is untouched.  Row status follows
-// mosaic_point_geom_to_cell: null rows MOSAIC_ROW_NULL; LineString, MultiLineString,
-// GeometryCollection, POINT EMPTY and undecodable rows MOSAIC_ROW_PATH; both hold an empty geometry.
+// pip_device.h, for the geometry types st_distance serves: Point, MultiPoint, LineString,
+// MultiLineString, Polygon, MultiPolygon.  A point is a part of kind kPartPoint with one ring of one
+// vertex; a component line is a part of kind kPartLine with one open ring of two or more vertices
+// (st_distance.h).  WKB rows are decoded with GeomBuilder's reader (either byte order, ISO Z/M and
+// EWKB flag variants); what the chip tables and mosaic_st_contains accept is untouched.  Row status
+// follows mosaic_point_geom_to_cell: null rows MOSAIC_ROW_NULL; GeometryCollection, POINT EMPTY and
+// undecodable rows MOSAIC_ROW_PATH; both hold an empty geometry.
+//
+// Lines are opt-in per column (`lines`, MOSAIC_GEOMS_LINES).  Without it a LineString /
+// MultiLineString WKB row is MOSAIC_ROW_PATH, as it was before the engine served lines: callers
+// that route such rows to the reference's row path keep doing so.  With it LINESTRING EMPTY and
+// MULTILINESTRING EMPTY are MOSAIC_ROW_OK rows without a facet (distance 0.0, like POLYGON EMPTY),
+// an empty member of a MultiLineString adds no part, and a component of exactly one vertex makes
+// the row MOSAIC_ROW_PATH (JTS cannot construct that LineString).
 #pragma once
 #include <stdint.h>
 
@@ -17,11 +25,11 @@
 
 namespace mosaic {
 
-enum { kPartPolygon = 0, kPartPoint = 1 };
 enum { kRowNull = 0, kRowOk = 1, kRowPath = 2 };  // MOSAIC_ROW_*
 
 struct GeomColumn {
     GeomBuilder b;
+    bool lines = false;  // decode WKB types 2 and 5 into line parts
     std::vector<uint8_t> part_kind;
     std::vector<int32_t> row_status;
     std::vector<uint32_t> geom_facets;
@@ -56,6 +64,35 @@ struct GeomColumn {
         if (!b.polygon(r, le, dims)) return false;
         part_kind.push_back(kPartPolygon);
         return true;
+    }
+    // the part of the vertices pushed since v0: one open ring.  No vertex: no part.  false: one vertex
+    bool close_line_part(size_t v0) {
+        const size_t n = b.verts.size() - v0;
+        if (n == 0) return true;
+        if (n == 1) return false;
+        pip::Box box = {INFINITY, INFINITY, -INFINITY, -INFINITY};
+        for (size_t i = v0; i < b.verts.size(); i++) {
+            box.minx = std::min(box.minx, b.verts[i].x);
+            box.maxx = std::max(box.maxx, b.verts[i].x);
+            box.miny = std::min(box.miny, b.verts[i].y);
+            box.maxy = std::max(box.maxy, b.verts[i].y);
+        }
+        b.ring_bbox.push_back(box);
+        b.ring_start.push_back((uint32_t)b.verts.size());
+        b.part_ring.push_back((uint32_t)b.ring_bbox.size());
+        part_kind.push_back(kPartLine);
+        return true;
+    }
+    bool line_part(GeomBuilder::Reader& r, bool le, int dims) {
+        const uint32_t npts = r.u32(le);
+        if (r.fail || (uint64_t)npts * 8 * dims > r.len - r.pos) return false;
+        const size_t v0 = b.verts.size();
+        for (uint32_t i = 0; i < npts; i++) {
+            const double x = r.f64(le), y = r.f64(le);
+            for (int d = 2; d < dims; d++) r.f64(le);
+            b.verts.push_back({x, y});
+        }
+        return !r.fail && close_line_part(v0);
     }
     // closes the row that began at mark m
     void end_row(const Mark& m, int32_t status) {
@@ -96,16 +133,19 @@ struct GeomColumn {
             return true;
         }
         if (type == 3) return polygon_part(r, le, dims);
-        if (type != 4 && type != 6) return false;
+        if (type == 2 && lines) return line_part(r, le, dims);
+        if (type != 4 && type != 6 && !(type == 5 && lines)) return false;
         const uint32_t n = r.u32(le);
         if (r.fail) return false;
         for (uint32_t k = 0; k < n; k++) {
             bool le2;
             uint32_t t2;
             int d2;
-            if (!GeomBuilder::header(r, le2, t2, d2) || t2 != (type == 4 ? 1u : 3u)) return false;
+            if (!GeomBuilder::header(r, le2, t2, d2) || t2 != (type == 4 ? 1u : type == 5 ? 2u : 3u)) return false;
             if (type == 6) {
                 if (!polygon_part(r, le2, d2)) return false;
+            } else if (type == 5) {
+                if (!line_part(r, le2, d2)) return false;
             } else {
                 if (!read_point(r, le2, d2, x, y)) return false;
                 if (!std::isnan(x) && !std::isnan(y)) point_part(x, y);  // an empty member adds no coordinate
@@ -154,6 +194,25 @@ struct GeomColumn {
                 part_kind.push_back(kPartPolygon);
             }
             end_row(m, kRowOk);
+        }
+        return true;
+    }
+    // a LineSet: geom_lines[n + 1], line_offsets, xy interleaved; false on inconsistent offsets.  A
+    // component of one vertex makes its row a row for the row path.
+    bool add_lines(int64_t n, const int64_t* geom_lines, const int64_t* line_offsets, const double* xy) {
+        for (int64_t g = 0; g < n; g++) {
+            const Mark m = mark();
+            if (geom_lines[g] < 0 || geom_lines[g + 1] < geom_lines[g]) return false;
+            bool ok = true;
+            for (int64_t l = geom_lines[g]; l < geom_lines[g + 1]; l++) {
+                if (line_offsets[l] < 0 || line_offsets[l + 1] < line_offsets[l]) return false;
+                if (!ok) continue;
+                const size_t v0 = b.verts.size();
+                for (int64_t i = line_offsets[l]; i < line_offsets[l + 1]; i++) b.verts.push_back({xy[2 * i], xy[2 * i + 1]});
+                ok = close_line_part(v0);
+            }
+            if (!ok) rollback(m);
+            end_row(m, ok ? kRowOk : kRowPath);
         }
         return true;
     }

@@ -24,7 +24,7 @@
 //     (self_match, same_geometry).  The comparison is exact, not a hash.  A WKB row in the other byte order decodes to the same flat
 //     content and is a self match; a ring rotated to another start vertex is not.  A null or
 //     row-path row (stored as an empty geometry) is never part of a self match: its pairs stay.
-//   * distance: the bits of dist::distance (st_distance.h); NaN when either row's status is not
+//   * distance: the bits of dist::distance with the part kinds (st_distance.h); NaN when either row's status is not
 //     MOSAIC_ROW_OK (mosaic_st_distance's convention).
 //   * Order: (landmark row, distance bits, candidate row).  The bits of a non-negative double order
 //     like a uint64, and a NaN's bits come after every number's.  Spark's row_number leaves ties
@@ -192,7 +192,7 @@ inline int neighbours(const CellIndexView& ix, const Col& L, const Col& C, const
         const uint32_t l = (uint32_t)(k >> 32), c = (uint32_t)k;
         if (!keep_self && self_match(L, l, C, c)) continue;
         const bool ok = L.status[l] == 1 && C.status[c] == 1;  // MOSAIC_ROW_OK
-        const double d = ok ? dist::distance(L.s, l, C.s, c) : std::numeric_limits<double>::quiet_NaN();
+        const double d = ok ? dist::distance(L.s, L.part_kind, l, C.s, C.part_kind, c) : std::numeric_limits<double>::quiet_NaN();
         rows.push_back(Row{l, bits_of(d), c});
     }
     std::sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {

@@ -1,18 +1,24 @@
 // JTS 1.19 `Geometry.distance` (DistanceOp.distance) for the geometry types this engine serves --
-// Point, MultiPoint, Polygon and MultiPolygon on either side -- on the host and on gfx950: the
+// Point, MultiPoint, LineString, MultiLineString, Polygon and MultiPolygon on either side -- on the
+// host and on gfx950: the
 // reference's st_distance (functions/MosaicContext.scala:146 ST_Distance ->
 // expressions/geometry/ST_Distance.scala:34-36 -> core/geometry/MosaicGeometryJTS.distance -> JTS
 // Geometry.distance; docs/source/api/spatial-functions.rst:416-471).
 //
 // Semantics (st_distance(g, h), g the left geometry):
 //   * either geometry empty (no coordinate)                                   -> 0.0
-//   * containment, in both directions: for each polygon part P of one side and each connected
-//     component of the other side (a point, or a polygon's shell), the component's first
-//     coordinate pt (ConnectedElementLocationFilter): locate_in_polygon(P, pt) != EXTERIOR -> 0.0.
-//     Boundary counts; each polygon part is located on its own (no MultiPolygon Mod-2 rule).
+//   * containment (computeContainmentDistance: PolygonExtracter x ConnectedElementLocationFilter),
+//     in both directions: for each polygon part P of one side and each connected component of the
+//     other side (a point, a component line, or a polygon's shell), the component's first
+//     coordinate pt: locate_in_polygon(P, pt) != EXTERIOR -> 0.0.  Boundary counts; each polygon
+//     part is located on its own (no MultiPolygon Mod-2 rule).  Only polygon parts can contain: a
+//     line part is a component and never a container, whether its first vertex equals its last or
+//     not (a point strictly inside a closed LineString is at a positive distance).
 //   * otherwise the minimum over (facets of g) x (facets of h) of segment_segment / point_segment /
 //     point_point below (Distance.segmentToSegment, Distance.pointToSegment, Coordinate.distance).
-//     Facets are every ring's segments, holes included, and every point.
+//     Facets are every ring's segments, holes included, every component line's segments
+//     (LinearComponentExtracter yields lines and polygon rings alike) and every point
+//     (PointExtracter).  A line of n >= 2 vertices has n - 1 segments: nothing closes it.
 // Every operation is one IEEE double operation in the order written (-ffp-contract=off).  `min` is
 // exact, so the result does not depend on the order the facet pairs are visited in: the kernels of
 // st_distance.hip, which prune and reorder, return the bits of the sequential driver `distance`.
@@ -21,7 +27,13 @@
 // single facet (v, v).  segment_segment on such a facet takes its A == B / C == D branches and is
 // then point_segment / point_point exactly, so the drivers treat every facet as a segment.  A
 // one-vertex ring never contains anything (locate_in_ring sees no segment), so point parts need no
-// special case in the containment step either.
+// special case in the containment step either.  A component line of a LineString /
+// MultiLineString is a part of kind kPartLine with one open ring of n >= 2 vertices; polygon rings
+// are stored closed (first == last), so "n - 1 segments per ring" serves both and no driver ever
+// adds a closing segment.  An open ring of two or more vertices would be a container to a driver
+// that does not know the part kinds, so the definition takes them: `distance` with the two
+// part_kind arrays.  The form without them treats every part as a possible container; it is the
+// same function on columns of points and polygons and is kept for those.
 //
 // Two caveats:
 //   * The arithmetic is restated from recall of JTS 1.19 (no JTS source or JVM was at hand), as
@@ -40,6 +52,11 @@
 #include "pip_device.h"
 
 namespace mosaic {
+
+// kind of a part of a geometry column (geoms_build.h): a polygon with its rings, a point (one ring
+// of one vertex), a component line (one open ring)
+enum { kPartPolygon = 0, kPartPoint = 1, kPartLine = 2 };
+
 namespace dist {
 
 using pip::Box;
@@ -134,17 +151,21 @@ MOSAIC_HD bool component_in_part(const GeomStore& sp, uint32_t p, const GeomStor
     const Vec2 pt = sq.verts[sq.ring_start[r]];
     return pip::locate_in_polygon(sp, p, pt.x, pt.y) != pip::LOC_EXTERIOR;
 }
-MOSAIC_HD bool contained(const GeomStore& sa, uint32_t a, const GeomStore& sb, uint32_t b) {
-    for (uint32_t p = sa.geom_part[a]; p < sa.geom_part[a + 1]; p++)
+// ka: the part kinds of sa, or null for "every part may contain" (columns without line parts)
+MOSAIC_HD bool contained(const GeomStore& sa, const uint8_t* ka, uint32_t a, const GeomStore& sb, uint32_t b) {
+    for (uint32_t p = sa.geom_part[a]; p < sa.geom_part[a + 1]; p++) {
+        if (ka && ka[p] != kPartPolygon) continue;
         for (uint32_t q = sb.geom_part[b]; q < sb.geom_part[b + 1]; q++)
             if (component_in_part(sa, p, sb, q)) return true;
+    }
     return false;
 }
 
-// The definition of the result: sequential and unpruned.
-MOSAIC_HD double distance(const GeomStore& sa, uint32_t g, const GeomStore& sb, uint32_t h) {
+// The definition of the result: sequential and unpruned.  ka / kb: the part kinds of the two columns.
+MOSAIC_HD double distance(const GeomStore& sa, const uint8_t* ka, uint32_t g, const GeomStore& sb, const uint8_t* kb,
+                          uint32_t h) {
     if (geom_facets(sa, g) == 0 || geom_facets(sb, h) == 0) return 0.0;
-    if (contained(sa, g, sb, h) || contained(sb, h, sa, g)) return 0.0;
+    if (contained(sa, ka, g, sb, h) || contained(sb, kb, h, sa, g)) return 0.0;
     uint32_t ra0, ra1, rb0, rb1;
     geom_rings(sa, g, ra0, ra1);
     geom_rings(sb, h, rb0, rb1);
@@ -167,6 +188,12 @@ MOSAIC_HD double distance(const GeomStore& sa, uint32_t g, const GeomStore& sb, 
         }
     }
     return m;
+}
+
+// The same for columns that hold points and polygons only: every part is taken as a possible
+// container (a one-vertex ring contains nothing).  Not for columns with line parts.
+MOSAIC_HD double distance(const GeomStore& sa, uint32_t g, const GeomStore& sb, uint32_t h) {
+    return distance(sa, nullptr, g, sb, nullptr, h);
 }
 
 // ---- pruning (st_distance.hip) ----

@@ -1,11 +1,15 @@
 // st_distance over device-resident geometry columns (mosaic_geoms_*, mosaic_st_distance): JTS
-// Geometry.distance for Point / MultiPoint / Polygon / MultiPolygon rows, on (left row, right row)
+// Geometry.distance for Point / MultiPoint / LineString / MultiLineString / Polygon / MultiPolygon
+// rows, on (left row, right row)
 // pairs -- step 3 of the reference's KNN iteration (models/knn/GridRingNeighbours.scala:153-156) and
 // the public ST_Distance (expressions/geometry/ST_Distance.scala:34-36).  st_distance.h holds the
 // semantics, the arithmetic and the sequential driver whose bits these kernels return.
 //
-// A column is the GeomStore layout of pip_device.h in HBM plus a kind per part (point / polygon), a
-// facet count per geometry and a status per row; it is immutable after creation.
+// A column is the GeomStore layout of pip_device.h in HBM plus a kind per part (point / polygon /
+// line), a facet count per geometry and a status per row; it is immutable after creation.  A line
+// part is one open ring: dist::ring_facets gives it n - 1 segments, a tile stages the vertices of its
+// own segments only (the index is clamped to the ring's last vertex), so no kernel forms a closing
+// segment, and only polygon parts are containers.
 //
 // Per call:
 //   k_dist_plan    one lane per pair: row range check, row status, work = facets(left) x facets(right);
@@ -13,9 +17,10 @@
 //                  others to its back (one atomicAdd per wave and list)
 //   k_dist_fill    status[] of every pair, NaN for the null / row-path ones (only after the host has
 //                  seen that no row index was out of range: such a call writes nothing)
-//   k_dist_small   one lane per pair: the sequential driver dist::distance
+//   k_dist_small   one lane per pair: the sequential driver dist::distance (with the part kinds)
 //   k_dist_block   one workgroup per pair.  Containment first, one lane per (polygon part, component)
-//                  and direction.  Then the side with fewer facets is staged in LDS, a tile of
+//                  and direction; a component is a point, a line part or a polygon's shell, located
+//                  by its first vertex.  Then the side with fewer facets is staged in LDS, a tile of
 //                  dist_tile segments at a time, and the other side's segments are streamed across the
 //                  lanes, each lane keeping a running minimum.  The workgroup's current minimum lives
 //                  in LDS as the bit pattern of a non-negative double (integer atomicMin); a
@@ -177,7 +182,7 @@ __global__ void __launch_bounds__(kBlock) k_dist_small(DistArgs a) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n_list; k += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = a.list[k];
         const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
-        a.out[i] = dist::distance(a.L.s, g, a.R.s, h);
+        a.out[i] = dist::distance(a.L.s, a.L.part_kind, g, a.R.s, a.R.part_kind, h);
     }
 }
 
@@ -349,14 +354,16 @@ extern "C" {
 
 uint64_t mosaic_layout_st_distance(void) { return dist::layout_fingerprint(); }
 
-int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb, const uint8_t* valid,
-                            mosaic_geoms** out) {
+int mosaic_geoms_create_wkb_ex(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb, const uint8_t* valid,
+                               uint32_t flags, mosaic_geoms** out) {
     if (!ctx || !out || n < 0 || (n > 0 && (!offsets || !wkb))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
+    if (flags & ~(uint32_t)MOSAIC_GEOMS_LINES) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: unknown flag");
     int device = 0, jdk = 8, n_cu = 256;
     void* stream = nullptr;
     SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
     GeomColumn c;
+    c.lines = (flags & MOSAIC_GEOMS_LINES) != 0;
     for (int64_t i = 0; i < n; i++) {
         if (offsets[i + 1] < offsets[i]) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: offsets decrease");
         if (valid && !valid[i])
@@ -364,6 +371,28 @@ int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, 
         else
             c.add_wkb(wkb + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     }
+    return upload_column(device, c, out);
+}
+
+int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb, const uint8_t* valid,
+                            mosaic_geoms** out) {
+    return mosaic_geoms_create_wkb_ex(ctx, n, offsets, wkb, valid, 0, out);
+}
+
+int mosaic_geoms_create_lines(mosaic_ctx* ctx, int64_t n, const int64_t* geom_lines, const int64_t* line_offsets,
+                              const double* xy, mosaic_geoms** out) {
+    if (!ctx || !out || n < 0 || !geom_lines || (n > 0 && !line_offsets)) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    *out = nullptr;
+    if (geom_lines[0] != 0) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
+    for (int64_t g = 0; g < n; g++)
+        if (geom_lines[g + 1] < geom_lines[g]) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
+    if (geom_lines[n] > 0 && !xy) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
+    int device = 0, jdk = 8, n_cu = 256;
+    void* stream = nullptr;
+    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    GeomColumn c;
+    c.lines = true;
+    if (!c.add_lines(n, geom_lines, line_offsets, xy)) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
     return upload_column(device, c, out);
 }
 

@@ -80,7 +80,8 @@ def _index_array(a):
 def grid_ring_neighbours(ctx, landmarks, candidates, cell_index, rows, cells, keep_self=False):
     """GridRingNeighbours.transform (models/knn/GridRingNeighbours.scala:121-160) for one iteration, on
     the context's GPU (mosaic_ring_neighbours).  ``landmarks`` / ``candidates``: ``GeometryTable``s or
-    anything ``geometry_table`` accepts; ``cell_index``: the candidates' ``CellIndex``; ``rows`` /
+    anything ``geometry_table`` accepts (a PolygonSet, a LineSet, points, WKB / WKT rows);
+    ``cell_index``: the candidates' ``CellIndex``; ``rows`` /
     ``cells``: one (landmark row, raw cell id) per row -- grid_geometrykringexplode(l, res, 1) in the
     first iteration, grid_geometrykloopexplode(l, res, i) in iteration i -- on the host or the device,
     duplicates allowed.
@@ -195,6 +196,8 @@ def knn_result(matches, k_neighbours, distance_threshold):
 def _side_kind(geoms, what):
     if hasattr(geoms, "geom_parts"):
         return "polygons"
+    if hasattr(geoms, "geom_lines"):
+        return "lines"
     arrays = (np.ndarray, list)
     if isinstance(geoms, tuple) and len(geoms) == 2 and all(isinstance(a, arrays) or _is_torch(a) for a in geoms):
         return "points"
@@ -202,19 +205,25 @@ def _side_kind(geoms, what):
         return "points"
     if _is_torch(geoms) and geoms.dim() == 2 and geoms.shape[1] == 2:
         return "points"
-    raise TypeError(f"SpatialKNN: {what} are a PolygonSet or a point column ((x, y) arrays or an [n, 2] array), "
-                    f"not {type(geoms).__name__}")
+    raise TypeError(f"SpatialKNN: {what} are a PolygonSet, a LineSet or a point column ((x, y) arrays or an "
+                    f"[n, 2] array), not {type(geoms).__name__}")
 
 
 class _Side:
     """One side of the model on the device: its geometry column and its chips at the index resolution
-    (grid_tessellateexplode(keepCoreGeometries = false), or one chip per point), both produced once."""
+    (grid_tessellateexplode(keepCoreGeometries = false); a LineSet's line chips, all non-core; or one
+    chip per point), both produced once."""
 
     def __init__(self, ctx, geoms, res):
         self.table = ctx.geometry_table(geoms)
         self.n = len(self.table)
         if hasattr(geoms, "geom_parts"):
             chips = tessellate(ctx.index_system, geoms, res, keep_core_geom=False, ctx=ctx)
+            self.is_core = np.array(chips["is_core"], np.uint8)
+            self.index_id = np.array(chips["index_id"], np.int64)
+            self.key = np.array(chips["polygon_key"], np.int32)
+        elif hasattr(geoms, "geom_lines"):
+            chips = tessellate(ctx.index_system, geoms, res, ctx=ctx, cells_only=True)
             self.is_core = np.array(chips["is_core"], np.uint8)
             self.index_id = np.array(chips["index_id"], np.int64)
             self.key = np.array(chips["polygon_key"], np.int32)
@@ -242,8 +251,10 @@ class SpatialKNN:
     """SpatialKNN (models/knn/SpatialKNN.scala) with ``approximate = true``: for every landmark, up to
     ``k_neighbours`` candidates found by growing grid rings, nearest first.
 
-    ``candidates`` / ``transform(landmarks)``: a PolygonSet or a point column (``(x, y)`` arrays or an
-    ``[n, 2]`` array); anything else raises TypeError.  The keywords are the reference's parameters
+    ``candidates`` / ``transform(landmarks)``: a PolygonSet, a LineSet or a point column (``(x, y)``
+    arrays or an ``[n, 2]`` array); anything else raises TypeError.  A LineSet side is indexed by its
+    line chips (Mosaic.lineFill); a line whose cells cross the antimeridian or a pole raises
+    MosaicError there, and the error is passed on.  The keywords are the reference's parameters
     (kNeighbours, indexResolution, maxIterations, earlyStopIterations, distanceThreshold, approximate).
     The candidates are tessellated and indexed once, at the first ``transform``; a landmark column's
     chips are produced once per ``transform`` and every iteration asks the k-ring (iteration 1) or the
