@@ -524,6 +524,58 @@ int mosaic_isect_geoms_export(const mosaic_isect_geoms* g, int32_t* left_key, in
                               uint8_t* status, int64_t* wkb_offsets, uint8_t* wkb);
 int mosaic_isect_geoms_destroy(mosaic_isect_geoms* g);
 
+/* ---- st_intersection_aggregate over the join of line chips with polygon chips ---- */
+/* "How much of each trip lies in each zone": one row per (line key, polygon key) whose chip sets share
+ * a cell id (the groups of mosaic_line_intersects_aggregate; a group exists even when its length is
+ * 0), sorted by key pair, with the length of the line inside the polygon -- and, from the geometry
+ * call, the pieces themselves (ST_IntersectionAggregate.scala:40-72 over a lineFill table).
+ * Increment per joined chip pair (csrc/line_clip.h is the definition):
+ *   polygon chip core   the whole line chip: every piece of at least 2 vertices (POINT / MULTIPOINT
+ *                       items contribute nothing); the polygon chip's geometry is not read, so a table
+ *                       built without core geometry serves
+ *   neither side core   clip(line chip, polygon chip): every segment is cut where llclip::meet finds
+ *                       it meeting a ring segment; an interval between consecutive cuts is kept iff
+ *                       its midpoint is not exterior to the polygon chip (the boundary counts: a
+ *                       stretch along a polygon edge is in the closed intersection, as in JTS) and
+ *                       contributes sqrt(dx * dx + dy * dy); maximal chains of kept intervals within a
+ *                       piece are the runs
+ *   line chip core      MOSAIC_E_ARG naming the first such chip that joins: lineFill never makes one,
+ *                       and the reference would union the polygon chip in, which is not a line result
+ * A group's length is the sum of its pairs' lengths in (cell id, line chip row, polygon chip row)
+ * order, each pair's in (piece, segment, interval) order: GPU, host and repeated calls agree bit for
+ * bit.  Its geometry is its runs in that order as JTS writes them (big-endian 2D): LINESTRING for one
+ * run, MULTILINESTRING for several, LINESTRING EMPTY (type 2, zero points) for none; a run is its first
+ * cut point, the original vertices in between (copied), its last cut point.
+ * Divergences from the reference (JTS intersection, then union): isolated touch points are not emitted
+ * (the union would carry a POINT); runs are not noded at ring vertices they pass, nor merged across
+ * cells (JTS's union does not line-merge either; no JTS output pins piece order or direction); a
+ * segment lying exactly along a side shared by two cells is in both cells' chips and is counted twice.
+ * On the GPU: k_lx_probe lists every chip pair with its cell (count, then fill: no guessed capacity),
+ * k_lx_chip_len the whole-chip lengths, k_lx_clip one wave per pair to clip.  A pair with a segment of
+ * more than kCutCap meet points is finished by the host driver (the same code and bits): no group is
+ * refused, the status column is 0 throughout.
+ * Errors as mosaic_line_intersects_aggregate: MOSAIC_E_ARG for tables of different grid / resolution or
+ * another device, MOSAIC_E_CAPACITY at 2^31 chip pairs and -- with *n_out = the required size -- when
+ * more than `cap` groups exist. */
+int mosaic_line_intersection_aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chips* polygons,
+                                       int32_t* out_line_key, int32_t* out_polygon_key, double* out_length, int64_t cap,
+                                       int64_t* n_out);
+/* The same with the geometry: read with mosaic_isect_geoms_info / _export (the area column holds the
+ * length, left key = line key, right key = polygon key), release with mosaic_isect_geoms_destroy. */
+int mosaic_line_intersection_aggregate_geometry(mosaic_ctx* ctx, const mosaic_line_chips* lines,
+                                                const mosaic_chips* polygons, mosaic_isect_geoms** out);
+/* The calling thread's last call of either: out = chip pairs, pairs clipped (no core side), pairs
+ * finished on the host (over the cut cap), run records of the clipped pairs, groups, kCutCap; ms =
+ * device time (HIP events) of k_lx_probe (both passes), of k_lx_chip_len + k_lx_clip (lengths and run
+ * counts) and of k_lx_clip's run fill pass (the geometry call). */
+int mosaic_line_intersection_last(int64_t out[6], double ms[3]);
+/* The same aggregate on the host, on at most 16 threads: no context, no GPU; the columns of
+ * mosaic_line_intersects_aggregate_host.  The GPU calls are tested against it bit for bit. */
+int mosaic_line_intersection_aggregate_host(int grid, int res, int64_t n_l, const uint8_t* l_core, const int64_t* l_cell,
+                                            const int32_t* l_key, const int64_t* l_off, const uint8_t* l_wkb, int64_t n_p,
+                                            const uint8_t* p_core, const int64_t* p_cell, const int32_t* p_key,
+                                            const int64_t* p_off, const uint8_t* p_wkb, mosaic_isect_geoms** out);
+
 /* ---- grid_cellkring / grid_cellkloop over a cell column (BNG, H3) ---- */
 /* loop = 0: kRing(cell, k); loop = 1: kLoop(cell, k).  Row i's cells go to out[i * stride ..] and
  * out_count[i] = their number (-1 for null rows, valid[i] == 0).  0 <= k <= 1000.

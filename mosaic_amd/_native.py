@@ -52,6 +52,8 @@ EXPORTS = [
     "mosaic_line_chips_create", "mosaic_line_chips_info", "mosaic_line_chips_destroy",
     "mosaic_line_intersects_aggregate", "mosaic_line_join_last", "mosaic_line_join_team",
     "mosaic_line_intersects_aggregate_host", "mosaic_geoms_create_wkb_ex", "mosaic_geoms_create_lines",
+    "mosaic_line_intersection_aggregate", "mosaic_line_intersection_aggregate_geometry",
+    "mosaic_line_intersection_last", "mosaic_line_intersection_aggregate_host",
 ]
 
 GEOM_WKB = 0
@@ -155,6 +157,11 @@ def lib():
         "mosaic_line_join_team": ([i32], i32),
         "mosaic_line_intersects_aggregate_host": ([i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64,
                                                    ctypes.POINTER(i64)], i32),
+        "mosaic_line_intersection_aggregate": ([vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),
+        "mosaic_line_intersection_aggregate_geometry": ([vp, vp, vp, ctypes.POINTER(vp)], i32),
+        "mosaic_line_intersection_last": ([vp, vp], i32),
+        "mosaic_line_intersection_aggregate_host": ([i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
+                                                     ctypes.POINTER(vp)], i32),
         "mosaic_tess_last_classify_ms": ([vp], ctypes.c_double),
         "mosaic_tess_counters": ([ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_point_to_cell_exact": ([vp, i32, vp, vp, i64, vp], i32),

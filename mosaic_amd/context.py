@@ -401,6 +401,49 @@ def line_intersects_aggregate_host(index_system, line_chips, polygon_chips, reso
         return lk[:k], pk[:k], fl[:k].astype(bool)
 
 
+def _export_isect_geoms(h):
+    """A mosaic_isect_geoms handle -> (left_key, right_key, area or length, status, wkb list); releases it."""
+    try:
+        n, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+        N.check(N.lib().mosaic_isect_geoms_info(h, ctypes.byref(n), ctypes.byref(nb)))
+        k = int(n.value)
+        lk = np.empty(k, np.int32)
+        rk = np.empty(k, np.int32)
+        ar = np.empty(k, np.float64)
+        st = np.empty(k, np.uint8)
+        off = np.empty(k + 1, np.int64)
+        data = np.empty(max(int(nb.value), 1), np.uint8)
+        N.check(N.lib().mosaic_isect_geoms_export(h, N.ptr(lk), N.ptr(rk), N.ptr(ar), N.ptr(st), N.ptr(off), N.ptr(data)))
+    finally:
+        N.lib().mosaic_isect_geoms_destroy(h)
+    wkb = [None if st[i] else bytes(data[off[i]:off[i + 1]]) for i in range(k)]
+    return lk, rk, ar, st, wkb
+
+
+def line_intersection_aggregate_host(index_system, line_chips, polygon_chips, resolution):
+    """st_intersection_aggregate over the join of line chips with polygon chips on the host
+    (mosaic_line_intersection_aggregate_host: no context, no GPU): the two chip dicts `tessellate`
+    returns -> (line_key int32, polygon_key int32, length float64, status uint8 (all 0), wkb list of
+    bytes), sorted by (line key, polygon key).  What MosaicContext.st_intersection_aggregate returns
+    for a LineChipTable and a ChipTable, bit for bit."""
+    if isinstance(index_system, str):
+        index_system = INDEX_SYSTEMS[index_system]()
+    res = index_system.get_resolution(resolution)
+
+    def cols(c):
+        off = np.ascontiguousarray(c["wkb"][0], dtype=np.int64)
+        data = np.ascontiguousarray(c["wkb"][1], dtype=np.uint8)
+        return (len(c["index_id"]), np.ascontiguousarray(c["is_core"], dtype=np.uint8),
+                np.ascontiguousarray(c["index_id"], dtype=np.int64), np.ascontiguousarray(c["polygon_key"], dtype=np.int32),
+                off if len(off) else np.zeros(1, np.int64), data if len(data) else np.zeros(1, np.uint8))
+
+    L, P = cols(line_chips), cols(polygon_chips)
+    h = ctypes.c_void_p()
+    N.check(N.lib().mosaic_line_intersection_aggregate_host(
+        index_system.grid, res, L[0], *[N.ptr(a) for a in L[1:]], P[0], *[N.ptr(a) for a in P[1:]], ctypes.byref(h)))
+    return _export_isect_geoms(h)
+
+
 _WKB_ROW_PATH = b"\x00\x00\x00\x00\x02\x00\x00\x00\x00"  # LINESTRING EMPTY: stands for a row the engine does not serve
 
 
@@ -1244,25 +1287,56 @@ class MosaicContext:
         chip join (MosaicContext st_intersection_aggregate -> ST_IntersectionAggregate.scala:40-72):
         (left_key int32, right_key int32, area float64, status uint8, wkb list of bytes) sorted by key
         pair.  The WKB is the union's polygonal part as JTS writes it (big-endian; POLYGON EMPTY when
-        the pieces have no area); status 1 = not answered (wkb None, area NaN): the row path."""
+        the pieces have no area); status 1 = not answered (wkb None, area NaN): the row path.
+
+        One side may be a LineChipTable: "how much of each trip lies in each zone"
+        (mosaic_line_intersection_aggregate_geometry).  The same 5-tuple with the length of the line
+        inside the polygon in place of the area, the pieces as LINESTRING / MULTILINESTRING (LINESTRING
+        EMPTY for none) and status 0 throughout.  With the line table on the right the key columns
+        come back swapped and sorted by (left key, right key) all the same.  Two line tables raise
+        ValueError."""
+        lines = (isinstance(left, LineChipTable), isinstance(right, LineChipTable))
+        if all(lines):
+            raise ValueError("st_intersection_aggregate: a line x line join is not served")
+        if lines[1]:
+            rk, lk, ln, st, wkb = self.st_intersection_aggregate(right, left)
+            order = np.lexsort((rk, lk))
+            return lk[order], rk[order], ln[order], st[order], [wkb[i] for i in order]
+        fn = N.lib().mosaic_line_intersection_aggregate_geometry if lines[0] else N.lib().mosaic_intersection_aggregate_geometry
         h = ctypes.c_void_p()
-        N.check(N.lib().mosaic_intersection_aggregate_geometry(self.handle, left.handle, right.handle, ctypes.byref(h)))
-        try:
-            n, nb = ctypes.c_int64(0), ctypes.c_int64(0)
-            N.check(N.lib().mosaic_isect_geoms_info(h, ctypes.byref(n), ctypes.byref(nb)))
-            k = int(n.value)
-            lk = np.empty(k, np.int32)
-            rk = np.empty(k, np.int32)
-            ar = np.empty(k, np.float64)
-            st = np.empty(k, np.uint8)
-            off = np.empty(k + 1, np.int64)
-            data = np.empty(max(int(nb.value), 1), np.uint8)
-            N.check(N.lib().mosaic_isect_geoms_export(h, N.ptr(lk), N.ptr(rk), N.ptr(ar), N.ptr(st), N.ptr(off),
-                                                      N.ptr(data)))
-        finally:
-            N.lib().mosaic_isect_geoms_destroy(h)
-        wkb = [None if st[i] else bytes(data[off[i]:off[i + 1]]) for i in range(k)]
-        return lk, rk, ar, st, wkb
+        N.check(fn(self.handle, left.handle, right.handle, ctypes.byref(h)))
+        return _export_isect_geoms(h)
+
+    def st_intersection_aggregate_length(self, left, right):
+        """st_length(st_intersection_aggregate(left_index, right_index)) per (left_key, right_key) group
+        of the join of a LineChipTable with a ChipTable (mosaic_line_intersection_aggregate): arrays
+        (left_key int32, right_key int32, length float64) sorted by key pair; the length column of
+        st_intersection_aggregate bit for bit, without the geometry.  With the line table on the right
+        the key columns come back swapped and sorted all the same."""
+        lines = (isinstance(left, LineChipTable), isinstance(right, LineChipTable))
+        if all(lines):
+            raise ValueError("st_intersection_aggregate_length: a line x line join is not served")
+        if not any(lines):
+            raise ValueError("st_intersection_aggregate_length: one side has to be a LineChipTable; two polygon "
+                             "tables have an area: st_intersection_aggregate_area")
+        if lines[1]:
+            rk, lk, ln = self.st_intersection_aggregate_length(right, left)
+            order = np.lexsort((rk, lk))
+            return lk[order], rk[order], ln[order]
+        cap = 1 << 16  # (a call that finds more groups reports the count and is repeated once)
+        while True:
+            lk = np.empty(cap, np.int32)
+            rk = np.empty(cap, np.int32)
+            ln = np.empty(cap, np.float64)
+            n_out = ctypes.c_int64(0)
+            rc = N.lib().mosaic_line_intersection_aggregate(self.handle, left.handle, right.handle, N.ptr(lk), N.ptr(rk),
+                                                            N.ptr(ln), cap, ctypes.byref(n_out))
+            if rc == N.MOSAIC_E_CAPACITY and n_out.value > cap:
+                cap = int(n_out.value)
+                continue
+            N.check(rc)
+            k = int(n_out.value)
+            return lk[:k], rk[:k], ln[:k]
 
     def st_intersection_aggregate_area(self, left, right):
         """st_area(st_intersection_aggregate(left_index, right_index)) per (left_key, right_key) group of
@@ -1270,6 +1344,9 @@ class MosaicContext:
         checks): arrays (left_key, right_key, area float64, status uint8) sorted by key pair; status 1
         marks groups the engine does not answer (a core chip without geometry, an overlay capacity
         exceeded)."""
+        if isinstance(left, LineChipTable) or isinstance(right, LineChipTable):
+            raise ValueError("st_intersection_aggregate_area: a line has no area; st_intersection_aggregate_length "
+                             "serves a LineChipTable")
         cap = 1 << 16  # (a call that finds more groups reports the count and is repeated once)
         while True:
             lk = np.empty(cap, np.int32)

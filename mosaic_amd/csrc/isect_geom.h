@@ -7,6 +7,18 @@
 
 #include <vector>
 
+// The result of an st_intersection_aggregate geometry call behind the C ABI's mosaic_isect_geoms handle
+// (mosaic_hip.hip fills it for two polygon tables, line_clip.hip / line_clip_host.cpp for a line table
+// against a polygon table, where `area` holds the length): groups sorted by key pair, group k's WKB at
+// wkb[off[k] .. off[k + 1]).
+struct mosaic_isect_geoms {
+    std::vector<int32_t> lk, rk;
+    std::vector<double> area;
+    std::vector<uint8_t> status;
+    std::vector<int64_t> off;
+    std::vector<uint8_t> wkb;
+};
+
 namespace mosaic {
 namespace isect_geom {
 

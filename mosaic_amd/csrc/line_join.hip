@@ -356,6 +356,21 @@ int mosaic_line_chips_info(const mosaic_line_chips* t, int64_t* out4) {
     return MOSAIC_OK;
 }
 
+// what k_lx_probe / k_lx_clip read from a line chip table, for line_clip.hip
+int mosaic_line_chips_view(const mosaic_line_chips* t, LineChipsView* out) {
+    if (!t || !out) return mosaic_tess_fail(MOSAIC_E_ARG, "null line chip table");
+    out->store = lineisect::LineStore{t->verts, t->piece_start, t->piece_bbox, t->chip_piece, t->chip_bbox};
+    out->cell = t->cell;
+    out->meta = t->meta;
+    out->grid = t->grid;
+    out->res = t->res;
+    out->device = t->device;
+    out->n_chips = t->n_chips;
+    out->n_pieces = t->n_pieces;
+    out->n_vertices = t->n_vertices;
+    return MOSAIC_OK;
+}
+
 int mosaic_line_chips_destroy(mosaic_line_chips* t) {
     if (!t) return MOSAIC_OK;
     (void)hipSetDevice(t->device);

@@ -92,6 +92,7 @@ extern "C" uint64_t mosaic_layout_join_stream(void);
 extern "C" uint64_t mosaic_layout_tess_clip(void);
 extern "C" uint64_t mosaic_layout_st_distance(void);
 extern "C" uint64_t mosaic_layout_ring_neighbours(void);
+extern "C" uint64_t mosaic_layout_line_clip(void);
 
 template <int GRID, bool LDS_COUNTS, bool PAIRS>
 __global__ void __launch_bounds__(256) k_join_raster(JoinArgs a) {
@@ -2550,7 +2551,8 @@ int mosaic_init(int device, mosaic_ctx** out) {
     if (mosaic_layout_join_binned() != mosaic_layout_fingerprint() || mosaic_layout_join_stream() != mosaic_layout_fingerprint() ||
         mosaic_layout_tess_clip() != mosaic::tessll::layout_fingerprint() ||
         mosaic_layout_st_distance() != mosaic::dist::layout_fingerprint() ||
-        mosaic_layout_ring_neighbours() != mosaic::rn::layout_fingerprint())
+        mosaic_layout_ring_neighbours() != mosaic::rn::layout_fingerprint() ||
+        mosaic_layout_line_clip() != mosaic::lineisect::clip_layout_fingerprint())
         return fail(MOSAIC_E_ARG, "libmosaic_hip.so links objects built against different struct layouts (rebuild every object)");
     thp_off_once();
     int count = 0;
@@ -5061,14 +5063,6 @@ static double agg_cell_edge(int grid, int res) {
                                        0.009415526, 0.003559893, 0.001348575, 0.000509713};
     return kEdgeKm[res < 0 ? 0 : (res > 15 ? 15 : res)] / 111.32;
 }
-
-struct mosaic_isect_geoms {
-    std::vector<int32_t> lk, rk;
-    std::vector<double> area;
-    std::vector<uint8_t> status;
-    std::vector<int64_t> off;
-    std::vector<uint8_t> wkb;
-};
 
 // The units of the chip join of two tables through the cell overlay; groups are runs of units with
 // one group slot (gstart), keyed by gkey[slot] = left key << 32 | right key.
