@@ -720,6 +720,23 @@ int mosaic_geoms_destroy(mosaic_geoms* geoms);
  * "dist_prune" (0: no pruning, same result). */
 int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
                        const int64_t* right_row, int64_t n_pairs, double* out, int32_t* status);
+/* out[i] = st_intersects(left[left_row[i]], right[right_row[i]]) as 1 or 0 (ST_Intersects.scala ->
+ * MosaicGeometryJTS.intersects -> JTS Geometry.intersects: the closed point sets share a point);
+ * left_row == right_row == NULL: row i with row i.  The value is that of the sequential definition in
+ * mosaic_amd/csrc/st_intersects.h: 0 when either geometry is empty (where mosaic_st_distance gives
+ * 0.0) or the geometry boxes do not meet, 1 when two facets meet or a polygon part of one side holds
+ * the first vertex of a component of the other (a line never holds anything), else 0.  The same
+ * row kinds are served as by mosaic_st_distance.
+ * status[i] (nullable): MOSAIC_ROW_OK; MOSAIC_ROW_NULL / MOSAIC_ROW_PATH as for mosaic_st_distance,
+ * out 0 on both.  A row index out of range: MOSAIC_E_ARG, nothing written.  out / status / the row
+ * arrays: host or device pointers.  Options: "dist_tile" and "dist_small_work" as for
+ * mosaic_st_distance (the same two decisions; no option of its own was measured to be needed);
+ * "dist_prune" does not apply: the blocks skipped here are skipped exactly. */
+int mosaic_st_intersects(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                         const int64_t* right_row, int64_t n_pairs, uint8_t* out, int32_t* status);
+/* the calling thread's last mosaic_st_intersects: pairs ended in the plan kernel (null, row-path, empty
+ * or box-disjoint), pairs served by one lane, pairs served by a workgroup (any may be null) */
+int mosaic_st_intersects_last_split(int64_t* ended_in_plan, int64_t* one_lane, int64_t* workgroup);
 
 /* ---- GridRingNeighbours: one iteration of the KNN model (models/knn/GridRingNeighbours.scala:121-160) ---- */
 /* The candidates' chips as a map from a cell to its sorted, distinct candidate rows: built once per chip

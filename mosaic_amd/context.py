@@ -882,6 +882,14 @@ class MosaicContext:
         null rows.  Rows either side leaves to the row path raise ``RowPathRequired`` with the pair
         indices, unless return_status, which adds the pairs' status array (ROW_OK / ROW_NULL /
         ROW_PATH; NaN on the row-path pairs too)."""
+        return self._pair_call("st_distance", N.lib().mosaic_st_distance, np.float64, left, right, pairs, return_status)
+
+    def _pair_call(self, name, entry, dtype, left, right, pairs, return_status):
+        """The argument handling that the pair functions over geometry columns share (st_distance,
+        st_intersects): the two sides as tables (built and closed here unless given as tables), the
+        row-wise form with a single geometry broadcast, or the pair list on the host or the device;
+        then ``entry(ctx, left, right, left_row, right_row, n, out, status)`` with a zeroed ``out`` of
+        ``dtype``.  Returns out (and status): row-path pairs raise unless return_status."""
         own = []
         try:
             tabs = []
@@ -900,7 +908,7 @@ class MosaicContext:
                     li = np.zeros(n, np.int64) if nl == 1 else np.arange(n, dtype=np.int64)
                     ri = np.zeros(n, np.int64) if nr == 1 else np.arange(n, dtype=np.int64)
                 else:
-                    raise ValueError(f"row-wise st_distance of {nl} and {nr} rows: the lengths must match "
+                    raise ValueError(f"row-wise {name} of {nl} and {nr} rows: the lengths must match "
                                      "(or one side is a single geometry)")
             else:
                 li, ri = pairs
@@ -916,10 +924,9 @@ class MosaicContext:
                 if len(li) != len(ri):
                     raise ValueError("pairs: the two index arrays have different lengths")
                 n = len(li)
-            out = np.zeros(n, np.float64)
+            out = np.zeros(n, dtype)
             status = np.zeros(n, np.int32)
-            N.check(N.lib().mosaic_st_distance(self.handle, lt.handle, rt.handle, N.ptr(li), N.ptr(ri), n, N.ptr(out),
-                                               N.ptr(status)))
+            N.check(entry(self.handle, lt.handle, rt.handle, N.ptr(li), N.ptr(ri), n, N.ptr(out), N.ptr(status)))
         finally:
             for t in own:
                 t.close()
@@ -929,6 +936,26 @@ class MosaicContext:
         if len(path):
             raise RowPathRequired(path)
         return out
+
+    def st_intersects(self, left, right, pairs=None, return_status=False):
+        """st_intersects(left, right) (functions/MosaicContext.scala ST_Intersects ->
+        expressions/geometry/ST_Intersects.scala -> core/geometry/MosaicGeometryJTS.intersects -> JTS
+        1.19 Geometry.intersects; python/mosaic/api/predicates.py) on this context's GPU
+        (mosaic_st_intersects): the two closed point sets share a point -- two facets meet
+        (RobustLineIntersector on CGAlgorithmsDD orientation signs), or a polygon part of one side holds
+        a component of the other (a line holds nothing, closed or not); the value of the sequential
+        definition in mosaic_amd/csrc/st_intersects.h.  An empty geometry intersects nothing (where
+        ``st_distance`` gives 0.0).  Point, MultiPoint, LineString, MultiLineString, Polygon and
+        MultiPolygon rows are served on either side.  It is the flat side of the reference's check of
+        ``st_intersects_aggregate`` (ST_IntersectsBehaviors.scala:45-68).
+
+        Arguments as for ``st_distance``: ``GeometryTable``s or anything ``geometry_table`` accepts;
+        ``pairs=None`` is row-wise, with a single geometry on one side broadcast;
+        ``pairs=(left_idx, right_idx)`` on the host or the device.  Returns a bool array, False on null
+        rows.  Rows either side leaves to the row path raise ``RowPathRequired`` with the pair
+        indices, unless return_status, which adds the pairs' status array (False on those pairs too)."""
+        res = self._pair_call("st_intersects", N.lib().mosaic_st_intersects, np.uint8, left, right, pairs, return_status)
+        return (res[0].astype(bool), res[1]) if return_status else res.astype(bool)
 
     # ---- the KNN model (mosaic_amd/knn.py) ----
     def cell_index(self, chips):

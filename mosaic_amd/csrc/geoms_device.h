@@ -1,5 +1,5 @@
 // The device-resident geometry column behind the C ABI's mosaic_geoms handle, shared by the translation
-// units that read one (st_distance.hip, ring_neighbours.hip): the GeomStore layout of pip_device.h in
+// units that read one (st_distance.hip, st_intersects.hip, ring_neighbours.hip): the GeomStore layout of pip_device.h in
 // HBM plus a kind per part (point / polygon), a facet count per geometry and a status per row.
 // Immutable after creation.  Also the small device-memory helpers those translation units share.
 #pragma once

@@ -39,6 +39,7 @@
 #include "../../include/mosaic_hip.h"
 #include "geoms_build.h"
 #include "geoms_device.h"
+#include "pair_lists.h"
 #include "st_distance.h"
 
 using namespace mosaic;
@@ -48,7 +49,11 @@ extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* smal
 
 namespace {
 
-constexpr int kBlock = 256;
+using pairs::blocks_for;
+using pairs::Col;
+using pairs::kBlock;
+using pairs::view;
+using pairs::wave_append;
 constexpr int kMaxTile = 1024;
 
 #define SD_RC(expr)          \
@@ -64,32 +69,8 @@ constexpr int kMaxTile = 1024;
                                     (std::string("st_distance: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
     } while (0)
 
-struct Col {
-    pip::GeomStore s;
-    const uint8_t* part_kind;
-    const uint32_t* facets;
-    const int32_t* status;
-    int64_t n;
-};
-
-Col view(const mosaic_geoms* g) {
-    return Col{pip::GeomStore{g->verts, g->ring_start, g->ring_bbox, g->part_ring, g->geom_part, g->geom_bbox},
-               g->part_kind, g->geom_facets, g->row_status, g->n_geoms};
-}
-
 using dev::DevMem;
 using dev::is_device_ptr;
-
-__device__ inline unsigned long long wave_append(unsigned long long* counter, bool pred) {
-    const unsigned long long m = __ballot(pred);
-    if (m == 0) return 0;
-    const int leader = __ffsll((long long)m) - 1;
-    const int lane = (int)__lane_id();
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-    base = (unsigned long long)__shfl((long long)base, leader, 64);
-    return base + (unsigned long long)__popcll(m & (((unsigned long long)1 << lane) - 1));
-}
 
 // a point column built on the device: row i is the point part (x[i], y[i]); a NaN coordinate is POINT EMPTY
 __global__ void __launch_bounds__(kBlock) k_points_col(const double* x, const double* y, int64_t n, pip::Vec2* verts,
@@ -345,8 +326,6 @@ int upload_column(int device, const GeomColumn& c, mosaic_geoms** out) {
     *out = g.release();
     return MOSAIC_OK;
 }
-
-int64_t blocks_for(int64_t n, int64_t cap) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
 
 }  // namespace
 
