@@ -13,8 +13,7 @@
 #include <vector>
 
 #include "../../include/mosaic_hip.h"
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);  // defined in mosaic_hip.hip
+#include "fail.h"
 
 extern "C" int mosaic_chip_table_create_arrays(mosaic_ctx* ctx, int grid, int res, int32_t n_polygons,
                                                const int64_t* chip_offsets, const uint8_t* is_core,

@@ -18,23 +18,13 @@
 // The host sizes the table before every round for the round's worst case (H3: 7 cells per frontier
 // cell; BNG: 8 j cells per border cell), so no insert can find it full; probe loops are bounded by
 // the capacity all the same.  One host sync per round reads the frontier and entry counts.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <stdint.h>
-
-#include <algorithm>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
 #include "cell_lists.h"
+#include "dev_rt.h"
 #include "geom_kring.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_gk_options(mosaic_ctx* ctx, int* table_log2, int64_t* max_cells);
 
 namespace {
 
@@ -223,57 +213,18 @@ __global__ void __launch_bounds__(256) k_gk_offsets(const uint64_t* sk, int64_t 
 }
 
 // ---- host ----
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    int reserve(size_t n) {
-        if (n <= bytes) return MOSAIC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        if (hipMalloc(&p, std::max<size_t>(n, 8)) != hipSuccess)
-            return mosaic_tess_fail(MOSAIC_E_NOMEM, ("hipMalloc(" + std::to_string(n) + ") failed").c_str());
-        bytes = std::max<size_t>(n, 8);
-        return MOSAIC_OK;
-    }
-    template <class T>
-    T* as() const {
-        return (T*)p;
-    }
-};
-
-#define GK_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            return mosaic_tess_fail(MOSAIC_E_HIP, (std::string(#expr ": ") + hipGetErrorString(_e)).c_str()); \
-    } while (0)
-#define GK_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-
-template <class T>
-int upload(Buf& b, const std::vector<T>& v, hipStream_t s) {
-    GK_RC(b.reserve(v.size() * sizeof(T)));
-    if (!v.empty()) GK_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return MOSAIC_OK;
-}
-
-int blocks_for(int64_t n, int n_cu) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)n_cu * 16)); }
+using dev::blocks_for;
+using dev::Buf;
+using dev::upload;
 
 struct DevTable {
     Buf keys, vals;
     uint64_t slots = 0;
     int alloc(uint64_t n, hipStream_t st) {
-        GK_RC(keys.reserve(n * 8));
-        GK_RC(vals.reserve(n * 4));
-        GK_TRY(hipMemsetAsync(keys.p, 0xff, n * 8, st));
-        GK_TRY(hipMemsetAsync(vals.p, 0xff, n * 4, st));
+        MOSAIC_RC(keys.reserve(n * 8));
+        MOSAIC_RC(vals.reserve(n * 4));
+        MOSAIC_HIP(hipMemsetAsync(keys.p, 0xff, n * 8, st));
+        MOSAIC_HIP(hipMemsetAsync(vals.p, 0xff, n * 4, st));
         slots = n;
         return MOSAIC_OK;
     }
@@ -298,12 +249,12 @@ int make_room(std::unique_ptr<DevTable>& tab, uint64_t entries, uint64_t more, c
     if (need == tab->slots) return MOSAIC_OK;
     if (need > lim.max_slots) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: more cells than option gk_max_cells allows");
     std::unique_ptr<DevTable> grown(new DevTable());
-    GK_RC(grown->alloc(need, st));
+    MOSAIC_RC(grown->alloc(need, st));
     if (entries > 0) {
-        hipLaunchKernelGGL(k_gk_rehash, dim3(blocks_for((int64_t)tab->slots, n_cu)), dim3(256), 0, st, tab->view(),
+        hipLaunchKernelGGL(k_gk_rehash, dim3(blocks_for((int64_t)tab->slots, 256, n_cu * 16)), dim3(256), 0, st, tab->view(),
                            grown->view(), flags);
-        GK_TRY(hipGetLastError());
-        GK_TRY(hipStreamSynchronize(st));  // the old table is freed below
+        MOSAIC_HIP(hipGetLastError());
+        MOSAIC_HIP(hipStreamSynchronize(st));  // the old table is freed below
     }
     tab.swap(grown);
     return MOSAIC_OK;
@@ -324,34 +275,27 @@ int run_batch(hipStream_t st, int n_cu, bool bng, int res, const Chips& ch, int6
         return MOSAIC_OK;
     }
     Buf d_core, d_id, d_geom, d_counts, d_flags, d_bad, d_f0, d_f1;
-    GK_RC(upload(d_core, ch.is_core, st));
-    GK_RC(upload(d_id, ch.id, st));
-    GK_RC(upload(d_geom, ch.geom, st));
-    GK_RC(d_counts.reserve(16));
-    GK_RC(d_flags.reserve(4));
-    GK_RC(d_bad.reserve((size_t)ng * 4));
-    GK_RC(d_f0.reserve((size_t)n * 8));
-    GK_TRY(hipMemsetAsync(d_counts.p, 0, 16, st));
-    GK_TRY(hipMemsetAsync(d_flags.p, 0, 4, st));
-    GK_TRY(hipMemsetAsync(d_bad.p, 0, (size_t)ng * 4, st));
+    MOSAIC_RC(upload(d_core, ch.is_core, st));
+    MOSAIC_RC(upload(d_id, ch.id, st));
+    MOSAIC_RC(upload(d_geom, ch.geom, st));
+    MOSAIC_RC(d_counts.reserve(16));
+    MOSAIC_RC(d_flags.reserve(4));
+    MOSAIC_RC(d_bad.reserve((size_t)ng * 4));
+    MOSAIC_RC(d_f0.reserve((size_t)n * 8));
+    MOSAIC_HIP(hipMemsetAsync(d_counts.p, 0, 16, st));
+    MOSAIC_HIP(hipMemsetAsync(d_flags.p, 0, 4, st));
+    MOSAIC_HIP(hipMemsetAsync(d_bad.p, 0, (size_t)ng * 4, st));
     if ((uint64_t)n > lim.max_slots) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: more cells than option gk_max_cells allows");
     std::unique_ptr<DevTable> tab(new DevTable());
     {
         const uint64_t slots = gk::slots_for((uint64_t)n, lim.first_slots);
         if (slots > lim.max_slots) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: more cells than option gk_max_cells allows");
-        GK_RC(tab->alloc(slots, st));
+        MOSAIC_RC(tab->alloc(slots, st));
     }
-    hipEvent_t e0, e1;
-    GK_TRY(hipEventCreate(&e0));
-    GK_TRY(hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
-        ~EvGuard() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-        }
-    } evg{e0, e1};
-    GK_TRY(hipEventRecord(e0, st));
+    dev::Events<2> ev;
+    MOSAIC_RC(ev.create());
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
+    MOSAIC_HIP(hipEventRecord(e0, st));
     Args a{};
     a.t = tab->view();
     a.bng = bng ? 1 : 0;
@@ -359,57 +303,57 @@ int run_batch(hipStream_t st, int n_cu, bool bng, int res, const Chips& ch, int6
     a.counts = d_counts.as<unsigned long long>();
     a.flags = d_flags.as<unsigned int>();
     a.bad = d_bad.as<int32_t>();
-    hipLaunchKernelGGL(k_gk_seed, dim3(blocks_for(n, n_cu)), dim3(256), 0, st, a, d_core.as<uint8_t>(), d_id.as<int64_t>(),
+    hipLaunchKernelGGL(k_gk_seed, dim3(blocks_for(n, 256, n_cu * 16)), dim3(256), 0, st, a, d_core.as<uint8_t>(), d_id.as<int64_t>(),
                        d_geom.as<int32_t>(), n, d_f0.as<uint64_t>());
-    GK_TRY(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long counts[2] = {0, 0};
-    GK_TRY(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
-    GK_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     int64_t f = (int64_t)counts[0];
     if (!bng) {
         Buf* cur = &d_f0;
         Buf* nxt = &d_f1;
         for (int round = 1; round <= k && f > 0; round++) {
             const uint64_t worst = 7 * (uint64_t)f;
-            GK_RC(make_room(tab, counts[1], worst, lim, a.flags, st, n_cu));
+            MOSAIC_RC(make_room(tab, counts[1], worst, lim, a.flags, st, n_cu));
             a.t = tab->view();
-            GK_RC(nxt->reserve((size_t)worst * 8));
-            GK_TRY(hipMemsetAsync(d_counts.p, 0, 8, st));
-            hipLaunchKernelGGL(k_gk_expand_h3, dim3(blocks_for(f, n_cu)), dim3(256), 0, st, a, cur->as<uint64_t>(), f, round,
+            MOSAIC_RC(nxt->reserve((size_t)worst * 8));
+            MOSAIC_HIP(hipMemsetAsync(d_counts.p, 0, 8, st));
+            hipLaunchKernelGGL(k_gk_expand_h3, dim3(blocks_for(f, 256, n_cu * 16)), dim3(256), 0, st, a, cur->as<uint64_t>(), f, round,
                                nxt->as<uint64_t>(), (int64_t)worst);
-            GK_TRY(hipGetLastError());
-            GK_TRY(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
-            GK_TRY(hipStreamSynchronize(st));
+            MOSAIC_HIP(hipGetLastError());
+            MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
+            MOSAIC_HIP(hipStreamSynchronize(st));
             f = (int64_t)counts[0];
             std::swap(cur, nxt);
         }
     } else {
         for (int j = 1; j <= k && f > 0; j++) {
-            GK_RC(make_room(tab, counts[1], 8 * (uint64_t)j * (uint64_t)f, lim, a.flags, st, n_cu));
+            MOSAIC_RC(make_room(tab, counts[1], 8 * (uint64_t)j * (uint64_t)f, lim, a.flags, st, n_cu));
             a.t = tab->view();
-            hipLaunchKernelGGL(k_gk_expand_bng, dim3(blocks_for(4 * f, n_cu)), dim3(256), 0, st, a, d_f0.as<uint64_t>(), f, j);
-            GK_TRY(hipGetLastError());
-            GK_TRY(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
-            GK_TRY(hipStreamSynchronize(st));
+            hipLaunchKernelGGL(k_gk_expand_bng, dim3(blocks_for(4 * f, 256, n_cu * 16)), dim3(256), 0, st, a, d_f0.as<uint64_t>(), f, j);
+            MOSAIC_HIP(hipGetLastError());
+            MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, st));
+            MOSAIC_HIP(hipStreamSynchronize(st));
         }
     }
     // the kept cells, sorted by (geometry, order key)
     const int64_t entries = (int64_t)counts[1];
     Buf d_sk0, d_sk1, d_rec0, d_rec1, d_off, d_tmp;
-    GK_RC(d_sk0.reserve((size_t)entries * 8));
-    GK_RC(d_sk1.reserve((size_t)entries * 8));
-    GK_RC(d_rec0.reserve((size_t)entries * 8));
-    GK_RC(d_rec1.reserve((size_t)entries * 8));
-    GK_RC(d_off.reserve((size_t)(ng + 1) * 8));
-    GK_TRY(hipMemsetAsync(d_counts.p, 0, 8, st));
-    GK_TRY(hipMemsetAsync(d_off.p, 0, (size_t)(ng + 1) * 8, st));
-    hipLaunchKernelGGL(k_gk_emit, dim3(blocks_for((int64_t)tab->slots, n_cu)), dim3(256), 0, st, a, k, loop,
+    MOSAIC_RC(d_sk0.reserve((size_t)entries * 8));
+    MOSAIC_RC(d_sk1.reserve((size_t)entries * 8));
+    MOSAIC_RC(d_rec0.reserve((size_t)entries * 8));
+    MOSAIC_RC(d_rec1.reserve((size_t)entries * 8));
+    MOSAIC_RC(d_off.reserve((size_t)(ng + 1) * 8));
+    MOSAIC_HIP(hipMemsetAsync(d_counts.p, 0, 8, st));
+    MOSAIC_HIP(hipMemsetAsync(d_off.p, 0, (size_t)(ng + 1) * 8, st));
+    hipLaunchKernelGGL(k_gk_emit, dim3(blocks_for((int64_t)tab->slots, 256, n_cu * 16)), dim3(256), 0, st, a, k, loop,
                        d_sk0.as<uint64_t>(), d_rec0.as<uint64_t>(), entries);
-    GK_TRY(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     unsigned int flags = 0;
-    GK_TRY(hipMemcpyAsync(counts, d_counts.p, 8, hipMemcpyDeviceToHost, st));
-    GK_TRY(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
-    GK_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     if (flags & 2u) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: device hash table overflow");
     if (flags & 4u) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: frontier overflow");
     const int64_t m = (int64_t)counts[0];
@@ -418,27 +362,20 @@ int run_batch(hipStream_t st, int n_cu, bool bng, int res, const Chips& ch, int6
     std::vector<int32_t> bad((size_t)ng, 0);
     if (m > 0) {
         if (m >= ((int64_t)1 << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry k-ring: result too large for one call");
-        size_t bytes = 0;
-        GK_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_sk0.as<uint64_t>(), d_sk1.as<uint64_t>(),
-                                                  d_rec0.as<uint64_t>(), d_rec1.as<uint64_t>(), (int)m, 0,
-                                                  gk::kSortKeyBits, st));
-        GK_RC(d_tmp.reserve(bytes));
-        bytes = d_tmp.bytes;
-        GK_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, bytes, d_sk0.as<uint64_t>(), d_sk1.as<uint64_t>(),
-                                                  d_rec0.as<uint64_t>(), d_rec1.as<uint64_t>(), (int)m, 0,
-                                                  gk::kSortKeyBits, st));
-        hipLaunchKernelGGL(k_gk_offsets, dim3(blocks_for(m, n_cu)), dim3(256), 0, st, d_sk1.as<uint64_t>(), m, (int)ng,
+        MOSAIC_RC(dev::sort_pairs(d_tmp, d_sk0.as<uint64_t>(), d_sk1.as<uint64_t>(), d_rec0.as<uint64_t>(), d_rec1.as<uint64_t>(),
+                                  (int)m, 0, gk::kSortKeyBits, st));
+        hipLaunchKernelGGL(k_gk_offsets, dim3(blocks_for(m, 256, n_cu * 16)), dim3(256), 0, st, d_sk1.as<uint64_t>(), m, (int)ng,
                            d_off.as<int64_t>());
-        GK_TRY(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    GK_TRY(hipEventRecord(e1, st));
+    MOSAIC_HIP(hipEventRecord(e1, st));
     if (m > 0) {
-        GK_TRY(hipMemcpyAsync(sk.data(), d_sk1.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        GK_TRY(hipMemcpyAsync(rec.data(), d_rec1.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        GK_TRY(hipMemcpyAsync(off.data(), d_off.p, (size_t)(ng + 1) * 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(sk.data(), d_sk1.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(rec.data(), d_rec1.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(off.data(), d_off.p, (size_t)(ng + 1) * 8, hipMemcpyDeviceToHost, st));
     }
-    GK_TRY(hipMemcpyAsync(bad.data(), d_bad.p, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
-    GK_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(bad.data(), d_bad.p, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     *device_ms += ms;
@@ -488,11 +425,11 @@ int mosaic_chips_kring(mosaic_ctx* ctx, int grid, int res, int64_t n_chips, cons
     for (int64_t i = 0; i < n_chips; i++)
         if (key[i] < 0 || key[i] >= n_geoms)
             return mosaic_tess_fail(MOSAIC_E_ARG, ("geometry k-ring: chip " + std::to_string(i) + " has a key outside [0, n_geoms)").c_str());
-    int device = 0, jdk = 8, n_cu = 256, log2 = 16;
+    int log2 = 16;
     int64_t max_cells = (int64_t)1 << 27;
-    void* stream = nullptr;
-    GK_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
-    GK_RC(mosaic_ctx_gk_options(ctx, &log2, &max_cells));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    MOSAIC_RC(mosaic_ctx_gk_options(ctx, &log2, &max_cells));
     const Limits lim{(uint64_t)1 << log2, (uint64_t)max_cells};
     const bool bng = grid == MOSAIC_GRID_BNG;
     const int64_t n_batches = (n_geoms + gk::kGeomBatch - 1) / gk::kGeomBatch;
@@ -507,7 +444,7 @@ int mosaic_chips_kring(mosaic_ctx* ctx, int grid, int res, int64_t n_chips, cons
     double ms = 0;
     for (int64_t b = 0; b < n_batches; b++) {
         const int64_t ng = std::min<int64_t>(gk::kGeomBatch, n_geoms - b * gk::kGeomBatch);
-        GK_RC(run_batch((hipStream_t)stream, n_cu, bng, res, batches[(size_t)b], ng, k, loop, lim, lists.get(), &ms));
+        MOSAIC_RC(run_batch(ex.stream, ex.n_cu, bng, res, batches[(size_t)b], ng, k, loop, lim, lists.get(), &ms));
     }
     g_last_ms = ms;
     *out = lists.release();
@@ -523,17 +460,17 @@ int mosaic_geometry_kring(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, c
         return mosaic_tess_fail(MOSAIC_E_ARG, loop ? "geometry k-loop: k must be in [1, 1000]"
                                                    : "geometry k-ring: k must be in [0, 1000]");
     mosaic_chip_set* cs = nullptr;
-    GK_RC(mosaic_tessellate_gpu(ctx, grid, res, n_geoms, geom_parts, part_rings, ring_offsets, xy, 0, 1, &cs));
+    MOSAIC_RC(mosaic_tessellate_gpu(ctx, grid, res, n_geoms, geom_parts, part_rings, ring_offsets, xy, 0, 1, &cs));
     struct SetGuard {
         mosaic_chip_set* s;
         ~SetGuard() { (void)mosaic_chip_set_destroy(s); }
     } guard{cs};
     int64_t n_chips = 0, wkb_bytes = 0;
-    GK_RC(mosaic_chip_set_info(cs, &n_chips, &wkb_bytes));
+    MOSAIC_RC(mosaic_chip_set_info(cs, &n_chips, &wkb_bytes));
     const uint8_t *is_core = nullptr, *wkb = nullptr;
     const int64_t *index_id = nullptr, *wkb_off = nullptr;
     const int32_t* key = nullptr;
-    GK_RC(mosaic_chip_set_columns(cs, &is_core, &index_id, &key, &wkb_off, &wkb));
+    MOSAIC_RC(mosaic_chip_set_columns(cs, &is_core, &index_id, &key, &wkb_off, &wkb));
     return mosaic_chips_kring(ctx, grid, res, n_chips, is_core, index_id, key, n_geoms, k, loop, out);
 }
 

@@ -26,17 +26,10 @@
 //                  run records at the offsets the counts give.
 // The host copies pairs, lengths and runs back and folds them (line_clip_host.h fold_groups): groups
 // sorted by key pair, each summed in (cell id, line chip row, polygon chip row) order.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
 #include "chips_view.h"
-#include "geoms_device.h"
+#include "dev_rt.h"
 #include "line_clip.h"
 #include "line_clip_host.h"
 
@@ -45,9 +38,6 @@ using lineisect::PairRec;
 using lineisect::Pt;
 using lineisect::Run;
 
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_exec(mosaic_ctx* ctx, int* device, void** stream, int* jdk, int* n_cu);
-
 namespace {
 
 constexpr int kBlock = 256;
@@ -55,20 +45,8 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kSlots = lineisect::kCutCap + 2;
 constexpr uint32_t kOverflowed = 0xffffffffu;
 
-#define LX_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define LX_HIP(expr)                                                                                                     \
-    do {                                                                                                                 \
-        hipError_t _e = (expr);                                                                                          \
-        if (_e != hipSuccess)                                                                                            \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                           \
-                                    (std::string("line intersection: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
+using dev::blocks_for;
+using dev::Buf;
 
 struct ProbeArgs {
     const int64_t* cell;  // the line chips
@@ -290,24 +268,14 @@ __global__ void __launch_bounds__(kBlock) k_lx_clip(ClipArgs a) {
     }
 }
 
-int64_t blocks_for(int64_t n, int64_t cap) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
-
 thread_local int64_t t_last[6] = {0, 0, 0, 0, 0, lineisect::kCutCap};
 thread_local double t_ms[3] = {0, 0, 0};
-
-struct Events {
-    hipEvent_t e[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 template <class T>
 int download(std::vector<T>& dst, const T* src, size_t n, hipStream_t stream) {
     dst.resize(n);
-    if (n) LX_HIP(hipMemcpyAsync(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, stream));
-    LX_HIP(hipStreamSynchronize(stream));
+    if (n) MOSAIC_HIP(hipMemcpyAsync(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     return MOSAIC_OK;
 }
 
@@ -322,14 +290,14 @@ struct HostGeoms {
 };
 int download_geoms(const ChipsJoinView& pv, HostGeoms& h, hipStream_t stream) {
     const size_t ng = (size_t)pv.n_chips;
-    LX_RC(download(h.geom_part, pv.store.geom_part, ng + 1, stream));
-    LX_RC(download(h.geom_bbox, pv.store.geom_bbox, ng, stream));
+    MOSAIC_RC(download(h.geom_part, pv.store.geom_part, ng + 1, stream));
+    MOSAIC_RC(download(h.geom_bbox, pv.store.geom_bbox, ng, stream));
     const size_t np = h.geom_part[ng];
-    LX_RC(download(h.part_ring, pv.store.part_ring, np + 1, stream));
+    MOSAIC_RC(download(h.part_ring, pv.store.part_ring, np + 1, stream));
     const size_t nr = h.part_ring[np];
-    LX_RC(download(h.ring_start, pv.store.ring_start, nr + 1, stream));
-    LX_RC(download(h.ring_bbox, pv.store.ring_bbox, nr, stream));
-    LX_RC(download(h.verts, pv.store.verts, (size_t)h.ring_start[nr], stream));
+    MOSAIC_RC(download(h.ring_start, pv.store.ring_start, nr + 1, stream));
+    MOSAIC_RC(download(h.ring_bbox, pv.store.ring_bbox, nr, stream));
+    MOSAIC_RC(download(h.verts, pv.store.verts, (size_t)h.ring_start[nr], stream));
     return MOSAIC_OK;
 }
 
@@ -344,14 +312,14 @@ struct HostLines {
 };
 int download_lines(const LineChipsView& lv, HostLines& h, bool boxes, hipStream_t stream) {
     if (!h.have) {
-        LX_RC(download(h.verts, lv.store.verts, (size_t)lv.n_vertices, stream));
-        LX_RC(download(h.piece_start, lv.store.piece_start, (size_t)lv.n_pieces + 1, stream));
-        LX_RC(download(h.chip_piece, lv.store.chip_piece, (size_t)lv.n_chips + 1, stream));
+        MOSAIC_RC(download(h.verts, lv.store.verts, (size_t)lv.n_vertices, stream));
+        MOSAIC_RC(download(h.piece_start, lv.store.piece_start, (size_t)lv.n_pieces + 1, stream));
+        MOSAIC_RC(download(h.chip_piece, lv.store.chip_piece, (size_t)lv.n_chips + 1, stream));
         h.have = true;
     }
     if (boxes && !h.boxes) {
-        LX_RC(download(h.piece_bbox, lv.store.piece_bbox, (size_t)lv.n_pieces, stream));
-        LX_RC(download(h.chip_bbox, lv.store.chip_bbox, (size_t)lv.n_chips, stream));
+        MOSAIC_RC(download(h.piece_bbox, lv.store.piece_bbox, (size_t)lv.n_pieces, stream));
+        MOSAIC_RC(download(h.chip_bbox, lv.store.chip_bbox, (size_t)lv.n_chips, stream));
         h.boxes = true;
     }
     return MOSAIC_OK;
@@ -361,29 +329,28 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
     out.off.assign(1, 0);
     LineChipsView lv;
     ChipsJoinView pv;
-    LX_RC(mosaic_line_chips_view(lines, &lv));
-    LX_RC(mosaic_chips_join_view(polygons, &pv));
+    MOSAIC_RC(mosaic_line_chips_view(lines, &lv));
+    MOSAIC_RC(mosaic_chips_join_view(polygons, &pv));
     if (lv.grid != pv.grid || lv.res != pv.res)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersection_aggregate: both chip tables must use the same grid and resolution");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    LX_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    if (lv.device != device || pv.device != device)
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    if (lv.device != ex.device || pv.device != ex.device)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersection_aggregate: a chip table of another device");
     std::fill(t_last, t_last + 5, 0);
     t_last[5] = lineisect::kCutCap;
     t_ms[0] = t_ms[1] = t_ms[2] = 0;
     if (lv.n_chips == 0 || pv.n_chips == 0 || pv.capacity == 0) return MOSAIC_OK;
-    hipStream_t stream = (hipStream_t)stream_v;
+    hipStream_t stream = ex.stream;
     const int64_t n = lv.n_chips;
-    const int64_t wide = (int64_t)n_cu * 16;
+    const int64_t wide = (int64_t)ex.n_cu * 16;
 
-    Events ev;
-    for (hipEvent_t& x : ev.e) LX_HIP(hipEventCreate(&x));
-    DevMem s_counts, s_list, s_chiplen, s_len, s_nruns, s_over, s_runoff, s_runs;
+    dev::Events<8> ev;
+    MOSAIC_RC(ev.create());
+    Buf s_counts, s_list, s_chiplen, s_len, s_nruns, s_over, s_runoff, s_runs;
     unsigned long long counts[7] = {0, 0, 0, 0, ~0ull, 0, 0};
-    LX_HIP(s_counts.alloc(sizeof(counts)));
-    LX_HIP(hipMemcpyAsync(s_counts.p, counts, sizeof(counts), hipMemcpyHostToDevice, stream));
+    MOSAIC_RC(s_counts.reserve(sizeof(counts)));
+    MOSAIC_HIP(hipMemcpyAsync(s_counts.p, counts, sizeof(counts), hipMemcpyHostToDevice, stream));
     ProbeArgs pa{};
     pa.cell = lv.cell;
     pa.meta = lv.meta;
@@ -393,13 +360,13 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
     pa.pmeta = pv.meta;
     pa.pass = 0;
     pa.counts = s_counts.as<unsigned long long>();
-    const dim3 pgrid((unsigned)blocks_for(n, wide));
-    LX_HIP(hipEventRecord(ev.e[0], stream));
+    const dim3 pgrid((unsigned)blocks_for(n, kBlock, wide));
+    MOSAIC_HIP(hipEventRecord(ev.e[0], stream));
     hipLaunchKernelGGL(k_lx_probe, pgrid, dim3(kBlock), 0, stream, pa);
-    LX_HIP(hipGetLastError());
-    LX_HIP(hipEventRecord(ev.e[1], stream));
-    LX_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    LX_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipEventRecord(ev.e[1], stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     const unsigned long long pairs = counts[0], n_clip = counts[1], n_core = pairs - n_clip;
     if (counts[4] != ~0ull)
         return mosaic_tess_fail(MOSAIC_E_ARG, ("st_intersection_aggregate (lines): line chip " + std::to_string(counts[4]) +
@@ -407,26 +374,26 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
                                                   .c_str());
     if (pairs == 0) return MOSAIC_OK;
     if (pairs >= (1ull << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "st_intersection_aggregate (lines): 2^31 chip pairs or more");
-    LX_HIP(s_list.alloc((size_t)pairs * sizeof(PairRec)));
+    MOSAIC_RC(s_list.reserve((size_t)pairs * sizeof(PairRec)));
     pa.pass = 1;
     pa.list = s_list.as<PairRec>();
     pa.n_pairs = pairs;
     pa.n_clip = n_clip;
-    LX_HIP(hipEventRecord(ev.e[2], stream));
+    MOSAIC_HIP(hipEventRecord(ev.e[2], stream));
     hipLaunchKernelGGL(k_lx_probe, pgrid, dim3(kBlock), 0, stream, pa);
-    LX_HIP(hipGetLastError());
-    LX_HIP(hipEventRecord(ev.e[3], stream));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipEventRecord(ev.e[3], stream));
     if (n_core) {
-        LX_HIP(s_chiplen.alloc((size_t)n * sizeof(double)));
-        hipLaunchKernelGGL(k_lx_chip_len, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, lv.store, n, s_chiplen.as<double>());
-        LX_HIP(hipGetLastError());
+        MOSAIC_RC(s_chiplen.reserve((size_t)n * sizeof(double)));
+        hipLaunchKernelGGL(k_lx_chip_len, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, lv.store, n, s_chiplen.as<double>());
+        MOSAIC_HIP(hipGetLastError());
     }
     ClipArgs ca{};
     const int64_t cblocks = std::max<int64_t>(1, std::min<int64_t>(((int64_t)n_clip + kWaves - 1) / kWaves, wide));
     if (n_clip) {
-        LX_HIP(s_len.alloc((size_t)n_clip * sizeof(double)));
-        LX_HIP(s_nruns.alloc((size_t)n_clip * sizeof(uint32_t)));
-        LX_HIP(s_over.alloc((size_t)n_clip * sizeof(uint32_t)));
+        MOSAIC_RC(s_len.reserve((size_t)n_clip * sizeof(double)));
+        MOSAIC_RC(s_nruns.reserve((size_t)n_clip * sizeof(uint32_t)));
+        MOSAIC_RC(s_over.reserve((size_t)n_clip * sizeof(uint32_t)));
         ca.L = lv.store;
         ca.P = pv.store;
         ca.list = pa.list;
@@ -437,22 +404,22 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
         ca.counts = pa.counts;
         ca.over = s_over.as<uint32_t>();
         hipLaunchKernelGGL(k_lx_clip, dim3((unsigned)cblocks), dim3(kBlock), 0, stream, ca);
-        LX_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    LX_HIP(hipEventRecord(ev.e[4], stream));
-    LX_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    LX_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipEventRecord(ev.e[4], stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     if (counts[2] != n_clip || counts[3] != n_core || counts[5] > n_clip)
         return mosaic_tess_fail(MOSAIC_E_CAPACITY, "st_intersection_aggregate (lines): the pair list does not match its count");
     const size_t n_over = (size_t)counts[5];
     std::vector<PairRec> hp;
     std::vector<double> len, chip_len;
     std::vector<uint32_t> n_runs, over;
-    LX_RC(download(hp, pa.list, (size_t)pairs, stream));
-    LX_RC(download(len, s_len.as<double>(), (size_t)n_clip, stream));
-    LX_RC(download(n_runs, s_nruns.as<uint32_t>(), (size_t)n_clip, stream));
-    LX_RC(download(over, s_over.as<uint32_t>(), n_over, stream));
-    if (n_core) LX_RC(download(chip_len, s_chiplen.as<double>(), (size_t)n, stream));
+    MOSAIC_RC(download(hp, pa.list, (size_t)pairs, stream));
+    MOSAIC_RC(download(len, s_len.as<double>(), (size_t)n_clip, stream));
+    MOSAIC_RC(download(n_runs, s_nruns.as<uint32_t>(), (size_t)n_clip, stream));
+    MOSAIC_RC(download(over, s_over.as<uint32_t>(), n_over, stream));
+    if (n_core) MOSAIC_RC(download(chip_len, s_chiplen.as<double>(), (size_t)n, stream));
     len.resize((size_t)pairs);
     for (size_t i = (size_t)n_clip; i < (size_t)pairs; i++) len[i] = chip_len[hp[i].line];
     // the pairs over the cut cap: the host driver on the tables' arrays
@@ -460,8 +427,8 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
     std::vector<std::vector<Run>> over_runs(n_over);
     if (n_over) {
         HostGeoms hg;
-        LX_RC(download_geoms(pv, hg, stream));
-        LX_RC(download_lines(lv, hl, true, stream));
+        MOSAIC_RC(download_geoms(pv, hg, stream));
+        MOSAIC_RC(download_lines(lv, hl, true, stream));
         const lineisect::LineStore L = hl.view();
         const pip::GeomStore P = hg.view();
         std::vector<Pt> cuts;
@@ -480,31 +447,31 @@ int aggregate(mosaic_ctx* ctx, const mosaic_line_chips* lines, const mosaic_chip
         run_off.assign((size_t)pairs + 1, 0);
         for (size_t k = 0; k < (size_t)n_clip; k++) run_off[k + 1] = run_off[k] + n_runs[k];
         for (size_t k = (size_t)n_clip; k < (size_t)pairs; k++) run_off[k + 1] = run_off[k];
-        LX_HIP(hipEventRecord(ev.e[5], stream));
+        MOSAIC_HIP(hipEventRecord(ev.e[5], stream));
         if (total_runs) {
             // the pairs the host finished keep the marker on the device: the fill pass skips them
-            LX_HIP(s_runoff.alloc(((size_t)n_clip + 1) * sizeof(unsigned long long)));
-            LX_HIP(s_runs.alloc((size_t)total_runs * sizeof(Run)));
-            LX_HIP(hipMemcpyAsync(s_runoff.p, run_off.data(), ((size_t)n_clip + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+            MOSAIC_RC(s_runoff.reserve(((size_t)n_clip + 1) * sizeof(unsigned long long)));
+            MOSAIC_RC(s_runs.reserve((size_t)total_runs * sizeof(Run)));
+            MOSAIC_HIP(hipMemcpyAsync(s_runoff.p, run_off.data(), ((size_t)n_clip + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
             ca.fill = 1;
             ca.run_off = s_runoff.as<unsigned long long>();
             ca.runs = s_runs.as<Run>();
             hipLaunchKernelGGL(k_lx_clip, dim3((unsigned)cblocks), dim3(kBlock), 0, stream, ca);
-            LX_HIP(hipGetLastError());
+            MOSAIC_HIP(hipGetLastError());
         }
-        LX_HIP(hipEventRecord(ev.e[6], stream));
-        LX_RC(download(runs, s_runs.as<Run>(), (size_t)total_runs, stream));
-        LX_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-        LX_HIP(hipStreamSynchronize(stream));
+        MOSAIC_HIP(hipEventRecord(ev.e[6], stream));
+        MOSAIC_RC(download(runs, s_runs.as<Run>(), (size_t)total_runs, stream));
+        MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+        MOSAIC_HIP(hipStreamSynchronize(stream));
         if (counts[6]) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "st_intersection_aggregate (lines): the run records do not match their count");
         for (size_t q = 0; q < n_over; q++) std::copy(over_runs[q].begin(), over_runs[q].end(), runs.begin() + (long)run_off[over[q]]);
-        LX_RC(download_lines(lv, hl, false, stream));
+        MOSAIC_RC(download_lines(lv, hl, false, stream));
     }
     float m01 = 0, m23 = 0, m34 = 0, m56 = 0;
-    LX_HIP(hipEventElapsedTime(&m01, ev.e[0], ev.e[1]));
-    LX_HIP(hipEventElapsedTime(&m23, ev.e[2], ev.e[3]));
-    LX_HIP(hipEventElapsedTime(&m34, ev.e[3], ev.e[4]));
-    if (geometry) LX_HIP(hipEventElapsedTime(&m56, ev.e[5], ev.e[6]));
+    MOSAIC_HIP(hipEventElapsedTime(&m01, ev.e[0], ev.e[1]));
+    MOSAIC_HIP(hipEventElapsedTime(&m23, ev.e[2], ev.e[3]));
+    MOSAIC_HIP(hipEventElapsedTime(&m34, ev.e[3], ev.e[4]));
+    if (geometry) MOSAIC_HIP(hipEventElapsedTime(&m56, ev.e[5], ev.e[6]));
     lineisect::fold_groups(hp.data(), hp.size(), len.data(), geometry, hl.view(), run_off.data(), runs.data(), out);
     t_last[0] = (int64_t)pairs;
     t_last[1] = (int64_t)n_clip;
@@ -536,7 +503,7 @@ int mosaic_line_intersection_aggregate(mosaic_ctx* ctx, const mosaic_line_chips*
         return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *n_out = 0;
     mosaic_isect_geoms g;
-    LX_RC(aggregate(ctx, lines, polygons, false, g));
+    MOSAIC_RC(aggregate(ctx, lines, polygons, false, g));
     *n_out = (int64_t)g.lk.size();
     if ((int64_t)g.lk.size() > cap)
         return mosaic_tess_fail(MOSAIC_E_CAPACITY, ("st_intersection_aggregate (lines): " + std::to_string(g.lk.size()) + " groups").c_str());
@@ -551,7 +518,7 @@ int mosaic_line_intersection_aggregate_geometry(mosaic_ctx* ctx, const mosaic_li
     if (!ctx || !lines || !polygons || !out) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
     std::unique_ptr<mosaic_isect_geoms> g(new mosaic_isect_geoms());
-    LX_RC(aggregate(ctx, lines, polygons, true, *g));
+    MOSAIC_RC(aggregate(ctx, lines, polygons, true, *g));
     *out = g.release();
     return MOSAIC_OK;
 }

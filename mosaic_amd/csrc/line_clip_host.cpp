@@ -13,13 +13,12 @@
 #include <vector>
 
 #include "../../include/mosaic_hip.h"
+#include "fail.h"
 #include "geom_build.h"
 #include "line_chips_build.h"
 #include "line_clip_host.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
 
 extern "C" int mosaic_line_intersection_aggregate_host(int grid, int res, int64_t n_l, const uint8_t* l_core, const int64_t* l_cell,
                                                        const int32_t* l_key, const int64_t* l_off, const uint8_t* l_wkb, int64_t n_p,

@@ -20,24 +20,14 @@
 //                 lineclip::build, first counting the chip's items, then, after a scan, writing them.
 //                 A chip of more than kItems pieces is built by the host routine.
 //   host          linefill::finish: the handed-off groups, the row order, the WKB.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <stdint.h>
-
-#include <algorithm>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
 #include "chip_set.h"
-#include "geoms_device.h"
+#include "dev_rt.h"
 #include "line_fill.h"
 
 using namespace mosaic;
 
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_exec(mosaic_ctx* ctx, int* device, void** stream, int* jdk, int* n_cu);
 extern "C" uint64_t mosaic_layout_lines_host(void);
 
 namespace {
@@ -45,20 +35,8 @@ namespace {
 constexpr int kBlock = 256;
 constexpr unsigned long long kNone = ~0ull;
 
-#define LF_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define LF_HIP(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess)                                                                                 \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                \
-                                    (std::string("line_fill: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
+using dev::blocks_for;
+using dev::Buf;
 
 struct Last {
     int64_t n[4] = {0, 0, 0, 0};
@@ -196,43 +174,6 @@ __global__ void __launch_bounds__(kBlock) k_line_clip(Batch b, const int64_t* g_
     }
 }
 
-unsigned blocks_for(int64_t n, int64_t lanes_cap) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, lanes_cap / kBlock));
-}
-
-// exclusive sums in place over n + 1 int64 (the last input is 0): a[n] = the total
-int scan_exclusive(int64_t* a, int64_t n1, DevMem& tmp, size_t& tmp_bytes, hipStream_t st) {
-    size_t bytes = 0;
-    LF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, a, a, (int)n1, st));
-    if (bytes > tmp_bytes) {
-        if (tmp.p) LF_HIP(hipFree(tmp.p));
-        tmp.p = nullptr;
-        LF_HIP(tmp.alloc(bytes));
-        tmp_bytes = bytes;
-    }
-    LF_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, a, a, (int)n1, st));
-    return MOSAIC_OK;
-}
-
-template <class K, class V>
-int sort_pairs(const K* k_in, K* k_out, const V* v_in, V* v_out, int64_t n, hipStream_t st) {
-    size_t bytes = 0;
-    DevMem tmp;
-    LF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k_in, k_out, v_in, v_out, (int)n, 0, (int)sizeof(K) * 8, st));
-    LF_HIP(tmp.alloc(bytes));
-    LF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, k_in, k_out, v_in, v_out, (int)n, 0, (int)sizeof(K) * 8, st));
-    LF_HIP(hipStreamSynchronize(st));  // (tmp is freed on return)
-    return MOSAIC_OK;
-}
-
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t v : e)
-            if (v) (void)hipEventDestroy(v);
-    }
-};
-
 constexpr int64_t kMaxRows = 0x7fffffff;
 
 }  // namespace
@@ -260,35 +201,33 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
         return mosaic_tess_fail(MOSAIC_E_RES, ("BNG resolution not supported; found " + std::to_string(res)).c_str());
     if (grid != MOSAIC_GRID_H3 && grid != MOSAIC_GRID_BNG) return mosaic_tess_fail(MOSAIC_E_ARG, "unknown grid");
     linefill::Clean c;
-    LF_RC(linefill::prepare(n_geoms, geom_lines, line_offsets, xy, c));
+    MOSAIC_RC(linefill::prepare(n_geoms, geom_lines, line_offsets, xy, c));
     g_last = Last();
     std::unique_ptr<mosaic_chip_set> cs(new mosaic_chip_set());
     if (c.n_verts == 0) {
         *out = cs.release();
         return MOSAIC_OK;
     }
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    LF_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    hipStream_t st = (hipStream_t)stream_v;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    hipStream_t st = ex.stream;
     const lineclip::Grid G{grid == MOSAIC_GRID_H3 ? 0 : 1, res};
     const int64_t nv = c.n_verts;
-    const int64_t light = (int64_t)n_cu * 2048, heavy = (int64_t)n_cu * 1024;  // lanes of the light / the walking kernels
-    Events ev;
-    for (auto& e : ev.e) LF_HIP(hipEventCreate(&e));
+    const int64_t light = (int64_t)ex.n_cu * 2048 / kBlock, heavy = (int64_t)ex.n_cu * 1024 / kBlock;  // blocks of the light / the walking kernels
+    dev::Events<4> ev;
+    MOSAIC_RC(ev.create());
 
-    DevMem d_xy, d_vl, d_lo, d_counters, d_spans, d_tmp;
-    size_t tmp_bytes = 0;
-    LF_HIP(d_xy.alloc((size_t)nv * 16));
-    LF_HIP(d_vl.alloc((size_t)nv * 4));
-    LF_HIP(d_lo.alloc((size_t)(c.n_lines + 1) * 8));
-    LF_HIP(d_counters.alloc(16));
-    LF_HIP(d_spans.alloc((size_t)(nv + 1) * 8));
-    LF_HIP(hipMemcpyAsync(d_xy.p, c.xy.data(), (size_t)nv * 16, hipMemcpyHostToDevice, st));
-    LF_HIP(hipMemcpyAsync(d_vl.p, c.vert_line.data(), (size_t)nv * 4, hipMemcpyHostToDevice, st));
-    LF_HIP(hipMemcpyAsync(d_lo.p, c.line_off.data(), (size_t)(c.n_lines + 1) * 8, hipMemcpyHostToDevice, st));
+    Buf d_xy, d_vl, d_lo, d_counters, d_spans, d_tmp;
+    MOSAIC_RC(d_xy.reserve((size_t)nv * 16));
+    MOSAIC_RC(d_vl.reserve((size_t)nv * 4));
+    MOSAIC_RC(d_lo.reserve((size_t)(c.n_lines + 1) * 8));
+    MOSAIC_RC(d_counters.reserve(16));
+    MOSAIC_RC(d_spans.reserve((size_t)(nv + 1) * 8));
+    MOSAIC_HIP(hipMemcpyAsync(d_xy.p, c.xy.data(), (size_t)nv * 16, hipMemcpyHostToDevice, st));
+    MOSAIC_HIP(hipMemcpyAsync(d_vl.p, c.vert_line.data(), (size_t)nv * 4, hipMemcpyHostToDevice, st));
+    MOSAIC_HIP(hipMemcpyAsync(d_lo.p, c.line_off.data(), (size_t)(c.n_lines + 1) * 8, hipMemcpyHostToDevice, st));
     unsigned long long counters[2] = {kNone, 0};
-    LF_HIP(hipMemcpyAsync(d_counters.p, counters, 16, hipMemcpyHostToDevice, st));
+    MOSAIC_HIP(hipMemcpyAsync(d_counters.p, counters, 16, hipMemcpyHostToDevice, st));
     const Batch B{G, d_xy.as<double>(), d_vl.as<int32_t>(), d_lo.as<int64_t>(), nv};
     auto read_counters = [&]() -> hipError_t {
         hipError_t e = hipMemcpyAsync(counters, d_counters.p, 16, hipMemcpyDeviceToHost, st);
@@ -296,14 +235,14 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
     };
 
     // ---- spans
-    LF_HIP(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(k_line_spans, dim3(blocks_for(nv + 1, heavy)), dim3(kBlock), 0, st, B, d_spans.as<int64_t>(),
+    MOSAIC_HIP(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_line_spans, dim3(blocks_for(nv + 1, kBlock, heavy)), dim3(kBlock), 0, st, B, d_spans.as<int64_t>(),
                        d_counters.as<unsigned long long>());
-    LF_HIP(hipGetLastError());
-    LF_RC(scan_exclusive(d_spans.as<int64_t>(), nv + 1, d_tmp, tmp_bytes, st));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_RC(dev::exclusive_sum(d_tmp, d_spans.as<int64_t>(), d_spans.as<int64_t>(), (int)(nv + 1), st));  // in place: the last input is 0, the last sum the total
     int64_t n_spans = 0;
-    LF_HIP(hipMemcpyAsync(&n_spans, d_spans.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, st));
-    LF_HIP(read_counters());
+    MOSAIC_HIP(hipMemcpyAsync(&n_spans, d_spans.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(read_counters());
     if (counters[0] != kNone) return linefill::fail_bad_cell(c, (int64_t)counters[0]);
     if (n_spans >= kMaxRows) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "line_fill: 2^31 - 1 spans at the most");
     int64_t n_segments = 0;
@@ -311,21 +250,21 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
     g_last.n[0] = n_segments;
 
     // ---- walk: count, scan, write
-    const unsigned walk_blocks = blocks_for(n_spans, heavy);
-    DevMem d_seen, d_cnt, d_status, d_slot;
-    LF_HIP(d_slot.alloc((size_t)n_spans * kSlot * 8));
-    LF_HIP(d_seen.alloc((size_t)walk_blocks * kBlock * lineclip::kWalkCap * 8));
-    LF_HIP(d_cnt.alloc((size_t)(n_spans + 1) * 8));
-    LF_HIP(d_status.alloc((size_t)n_spans));
-    LF_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_spans + 1) * 8, st));
+    const unsigned walk_blocks = blocks_for(n_spans, kBlock, heavy);
+    Buf d_seen, d_cnt, d_status, d_slot;
+    MOSAIC_RC(d_slot.reserve((size_t)n_spans * kSlot * 8));
+    MOSAIC_RC(d_seen.reserve((size_t)walk_blocks * kBlock * lineclip::kWalkCap * 8));
+    MOSAIC_RC(d_cnt.reserve((size_t)(n_spans + 1) * 8));
+    MOSAIC_RC(d_status.reserve((size_t)n_spans));
+    MOSAIC_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_spans + 1) * 8, st));
     hipLaunchKernelGGL((k_line_walk<false>), dim3(walk_blocks), dim3(kBlock), 0, st, B, d_spans.as<int64_t>(), n_spans,
                        d_seen.as<int64_t>(), d_cnt.as<int64_t>(), d_status.as<uint8_t>(), d_counters.as<unsigned long long>(),
                        d_slot.as<uint64_t>(), (uint64_t*)nullptr, (uint32_t*)nullptr);
-    LF_HIP(hipGetLastError());
-    LF_RC(scan_exclusive(d_cnt.as<int64_t>(), n_spans + 1, d_tmp, tmp_bytes, st));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_RC(dev::exclusive_sum(d_tmp, d_cnt.as<int64_t>(), d_cnt.as<int64_t>(), (int)(n_spans + 1), st));
     int64_t n_dev_pairs = 0;
-    LF_HIP(hipMemcpyAsync(&n_dev_pairs, d_cnt.as<int64_t>() + n_spans, 8, hipMemcpyDeviceToHost, st));
-    LF_HIP(read_counters());
+    MOSAIC_HIP(hipMemcpyAsync(&n_dev_pairs, d_cnt.as<int64_t>() + n_spans, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(read_counters());
     if (counters[0] != kNone) return linefill::fail_bad_cell(c, (int64_t)counters[0]);
     // spans for the host
     std::vector<uint64_t> extra_cell;
@@ -333,9 +272,9 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
     if (counters[1]) {
         std::vector<uint8_t> status((size_t)n_spans);
         std::vector<int64_t> span_off((size_t)nv + 1);
-        LF_HIP(hipMemcpyAsync(status.data(), d_status.p, (size_t)n_spans, hipMemcpyDeviceToHost, st));
-        LF_HIP(hipMemcpyAsync(span_off.data(), d_spans.p, (size_t)(nv + 1) * 8, hipMemcpyDeviceToHost, st));
-        LF_HIP(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipMemcpyAsync(status.data(), d_status.p, (size_t)n_spans, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(span_off.data(), d_spans.p, (size_t)(nv + 1) * 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
         std::vector<int64_t> cells;
         for (int64_t i = 0; i < n_spans; i++) {
             if (status[(size_t)i] != lineclip::kNeedsMore) continue;
@@ -347,7 +286,7 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
             for (int64_t cell : cells) extra_cell.push_back((uint64_t)cell), extra_seg.push_back((uint32_t)s);
         }
         counters[1] = 0;
-        LF_HIP(hipMemcpyAsync(d_counters.as<unsigned long long>() + 1, &counters[1], 8, hipMemcpyHostToDevice, st));
+        MOSAIC_HIP(hipMemcpyAsync(d_counters.as<unsigned long long>() + 1, &counters[1], 8, hipMemcpyHostToDevice, st));
     }
     const int64_t n_pairs = n_dev_pairs + (int64_t)extra_cell.size();
     g_last.n[3] = n_pairs;
@@ -356,98 +295,88 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
         *out = cs.release();
         return MOSAIC_OK;
     }
-    DevMem d_cell0, d_cell1, d_seg0, d_seg1;
-    LF_HIP(d_cell0.alloc((size_t)n_pairs * 8));
-    LF_HIP(d_cell1.alloc((size_t)n_pairs * 8));
-    LF_HIP(d_seg0.alloc((size_t)n_pairs * 4));
-    LF_HIP(d_seg1.alloc((size_t)n_pairs * 4));
+    Buf d_cell0, d_cell1, d_seg0, d_seg1;
+    MOSAIC_RC(d_cell0.reserve((size_t)n_pairs * 8));
+    MOSAIC_RC(d_cell1.reserve((size_t)n_pairs * 8));
+    MOSAIC_RC(d_seg0.reserve((size_t)n_pairs * 4));
+    MOSAIC_RC(d_seg1.reserve((size_t)n_pairs * 4));
     hipLaunchKernelGGL((k_line_walk<true>), dim3(walk_blocks), dim3(kBlock), 0, st, B, d_spans.as<int64_t>(), n_spans,
                        d_seen.as<int64_t>(), d_cnt.as<int64_t>(), d_status.as<uint8_t>(), d_counters.as<unsigned long long>(),
                        d_slot.as<uint64_t>(), d_cell0.as<uint64_t>(), d_seg0.as<uint32_t>());
-    LF_HIP(hipGetLastError());
-    LF_HIP(hipEventRecord(ev.e[1], st));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipEventRecord(ev.e[1], st));
 
     // ---- groups
     if (!extra_cell.empty()) {
-        LF_HIP(hipMemcpyAsync(d_cell0.as<uint64_t>() + n_dev_pairs, extra_cell.data(), extra_cell.size() * 8, hipMemcpyHostToDevice, st));
-        LF_HIP(hipMemcpyAsync(d_seg0.as<uint32_t>() + n_dev_pairs, extra_seg.data(), extra_seg.size() * 4, hipMemcpyHostToDevice, st));
-        LF_RC(sort_pairs(d_seg0.as<uint32_t>(), d_seg1.as<uint32_t>(), d_cell0.as<uint64_t>(), d_cell1.as<uint64_t>(), n_pairs, st));
+        MOSAIC_HIP(hipMemcpyAsync(d_cell0.as<uint64_t>() + n_dev_pairs, extra_cell.data(), extra_cell.size() * 8, hipMemcpyHostToDevice, st));
+        MOSAIC_HIP(hipMemcpyAsync(d_seg0.as<uint32_t>() + n_dev_pairs, extra_seg.data(), extra_seg.size() * 4, hipMemcpyHostToDevice, st));
+        MOSAIC_RC(dev::sort_pairs(d_tmp, d_seg0.as<uint32_t>(), d_seg1.as<uint32_t>(), d_cell0.as<uint64_t>(), d_cell1.as<uint64_t>(), (int)n_pairs, 0, 32, st));
         std::swap(d_seg0.p, d_seg1.p);
         std::swap(d_cell0.p, d_cell1.p);
     }
-    LF_RC(sort_pairs(d_cell0.as<uint64_t>(), d_cell1.as<uint64_t>(), d_seg0.as<uint32_t>(), d_seg1.as<uint32_t>(), n_pairs, st));
+    MOSAIC_RC(dev::sort_pairs(d_tmp, d_cell0.as<uint64_t>(), d_cell1.as<uint64_t>(), d_seg0.as<uint32_t>(), d_seg1.as<uint32_t>(), (int)n_pairs, 0, 64, st));
     const uint64_t* s_cell = d_cell1.as<uint64_t>();
     const uint32_t* s_seg = d_seg1.as<uint32_t>();
     uint64_t* flags = d_cell0.as<uint64_t>();  // (the unsorted keys are done with)
-    hipLaunchKernelGGL(k_line_flags, dim3(blocks_for(n_pairs, light)), dim3(kBlock), 0, st, s_cell, s_seg, B.vert_line, n_pairs, flags);
-    LF_HIP(hipGetLastError());
-    {
-        size_t bytes = 0;
-        LF_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, flags, flags, (int)n_pairs, st));
-        if (bytes > tmp_bytes) {
-            if (d_tmp.p) LF_HIP(hipFree(d_tmp.p));
-            d_tmp.p = nullptr;
-            LF_HIP(d_tmp.alloc(bytes));
-            tmp_bytes = bytes;
-        }
-        LF_HIP(hipcub::DeviceScan::InclusiveSum(d_tmp.p, bytes, flags, flags, (int)n_pairs, st));
-    }
+    hipLaunchKernelGGL(k_line_flags, dim3(blocks_for(n_pairs, kBlock, light)), dim3(kBlock), 0, st, s_cell, s_seg, B.vert_line, n_pairs, flags);
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_RC(dev::inclusive_sum(d_tmp, flags, flags, (int)n_pairs, st));
     uint64_t last = 0;
-    LF_HIP(hipMemcpyAsync(&last, flags + (n_pairs - 1), 8, hipMemcpyDeviceToHost, st));
-    LF_HIP(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(&last, flags + (n_pairs - 1), 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     const int64_t n_groups = (int64_t)(last >> 32), n_useg = (int64_t)(last & 0xffffffffull);
     g_last.n[1] = n_groups;
-    DevMem d_gcell, d_gstart, d_useg;
-    LF_HIP(d_gcell.alloc((size_t)n_groups * 8));
-    LF_HIP(d_gstart.alloc((size_t)(n_groups + 1) * 8));
-    LF_HIP(d_useg.alloc((size_t)n_useg * 4));
-    hipLaunchKernelGGL(k_line_fill, dim3(blocks_for(n_pairs, light)), dim3(kBlock), 0, st, s_cell, s_seg, flags, n_pairs,
+    Buf d_gcell, d_gstart, d_useg;
+    MOSAIC_RC(d_gcell.reserve((size_t)n_groups * 8));
+    MOSAIC_RC(d_gstart.reserve((size_t)(n_groups + 1) * 8));
+    MOSAIC_RC(d_useg.reserve((size_t)n_useg * 4));
+    hipLaunchKernelGGL(k_line_fill, dim3(blocks_for(n_pairs, kBlock, light)), dim3(kBlock), 0, st, s_cell, s_seg, flags, n_pairs,
                        d_gcell.as<int64_t>(), d_gstart.as<int64_t>(), d_useg.as<uint32_t>());
-    LF_HIP(hipGetLastError());
-    LF_HIP(hipMemcpyAsync(d_gstart.as<int64_t>() + n_groups, &n_useg, 8, hipMemcpyHostToDevice, st));
-    LF_HIP(hipEventRecord(ev.e[2], st));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemcpyAsync(d_gstart.as<int64_t>() + n_groups, &n_useg, 8, hipMemcpyHostToDevice, st));
+    MOSAIC_HIP(hipEventRecord(ev.e[2], st));
 
     // ---- clip: count, scan, write
-    const unsigned clip_blocks = blocks_for(n_groups, heavy);
-    DevMem d_work, d_recs, d_icnt, d_items;
-    LF_HIP(d_work.alloc((size_t)clip_blocks * kBlock * lineclip::kItems * sizeof(lineclip::Item)));
-    LF_HIP(d_recs.alloc((size_t)n_groups * sizeof(linefill::GroupRec)));
-    LF_HIP(d_icnt.alloc((size_t)(n_groups + 1) * 8));
-    LF_HIP(hipMemsetAsync(d_icnt.p, 0, (size_t)(n_groups + 1) * 8, st));
+    const unsigned clip_blocks = blocks_for(n_groups, kBlock, heavy);
+    Buf d_work, d_recs, d_icnt, d_items;
+    MOSAIC_RC(d_work.reserve((size_t)clip_blocks * kBlock * lineclip::kItems * sizeof(lineclip::Item)));
+    MOSAIC_RC(d_recs.reserve((size_t)n_groups * sizeof(linefill::GroupRec)));
+    MOSAIC_RC(d_icnt.reserve((size_t)(n_groups + 1) * 8));
+    MOSAIC_HIP(hipMemsetAsync(d_icnt.p, 0, (size_t)(n_groups + 1) * 8, st));
     hipLaunchKernelGGL((k_line_clip<false>), dim3(clip_blocks), dim3(kBlock), 0, st, B, d_gcell.as<int64_t>(), d_gstart.as<int64_t>(),
                        d_useg.as<uint32_t>(), n_groups, d_work.as<lineclip::Item>(), d_recs.as<linefill::GroupRec>(),
                        d_icnt.as<int64_t>(), d_counters.as<unsigned long long>(), (lineclip::Item*)nullptr);
-    LF_HIP(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     int64_t n_items = 0;
     if (!cells_only) {
-        LF_RC(scan_exclusive(d_icnt.as<int64_t>(), n_groups + 1, d_tmp, tmp_bytes, st));
-        LF_HIP(hipMemcpyAsync(&n_items, d_icnt.as<int64_t>() + n_groups, 8, hipMemcpyDeviceToHost, st));
-        LF_HIP(hipStreamSynchronize(st));
-        LF_HIP(d_items.alloc((size_t)n_items * sizeof(lineclip::Item)));
+        MOSAIC_RC(dev::exclusive_sum(d_tmp, d_icnt.as<int64_t>(), d_icnt.as<int64_t>(), (int)(n_groups + 1), st));
+        MOSAIC_HIP(hipMemcpyAsync(&n_items, d_icnt.as<int64_t>() + n_groups, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
+        MOSAIC_RC(d_items.reserve((size_t)n_items * sizeof(lineclip::Item)));
         hipLaunchKernelGGL((k_line_clip<true>), dim3(clip_blocks), dim3(kBlock), 0, st, B, d_gcell.as<int64_t>(), d_gstart.as<int64_t>(),
                            d_useg.as<uint32_t>(), n_groups, d_work.as<lineclip::Item>(), d_recs.as<linefill::GroupRec>(),
                            d_icnt.as<int64_t>(), d_counters.as<unsigned long long>(), d_items.as<lineclip::Item>());
-        LF_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    LF_HIP(hipEventRecord(ev.e[3], st));
+    MOSAIC_HIP(hipEventRecord(ev.e[3], st));
     std::vector<linefill::GroupRec> recs((size_t)n_groups);
     std::vector<int64_t> seg_start((size_t)n_groups + 1);
     std::vector<uint32_t> useg((size_t)n_useg);
     std::vector<lineclip::Item> items((size_t)std::max<int64_t>(1, n_items));
-    LF_HIP(hipMemcpyAsync(recs.data(), d_recs.p, (size_t)n_groups * sizeof(linefill::GroupRec), hipMemcpyDeviceToHost, st));
-    LF_HIP(hipMemcpyAsync(seg_start.data(), d_gstart.p, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, st));
-    LF_HIP(hipMemcpyAsync(useg.data(), d_useg.p, (size_t)n_useg * 4, hipMemcpyDeviceToHost, st));
-    if (n_items) LF_HIP(hipMemcpyAsync(items.data(), d_items.p, (size_t)n_items * sizeof(lineclip::Item), hipMemcpyDeviceToHost, st));
-    LF_HIP(read_counters());
+    MOSAIC_HIP(hipMemcpyAsync(recs.data(), d_recs.p, (size_t)n_groups * sizeof(linefill::GroupRec), hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(seg_start.data(), d_gstart.p, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(useg.data(), d_useg.p, (size_t)n_useg * 4, hipMemcpyDeviceToHost, st));
+    if (n_items) MOSAIC_HIP(hipMemcpyAsync(items.data(), d_items.p, (size_t)n_items * sizeof(lineclip::Item), hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(read_counters());
     if (counters[0] != kNone) return linefill::fail_bad_cell(c, (int64_t)counters[0]);
     g_last.n[2] = (int64_t)counters[1];
     for (int i = 0; i < 3; i++) {
         float ms = 0;
-        LF_HIP(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
+        MOSAIC_HIP(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
         g_last.ms[i] = ms;
     }
     int64_t bad = -1;
-    LF_RC(linefill::finish(G, c, n_groups, recs.data(), seg_start.data(), useg.data(), items.data(), cells_only, cs.get(), &bad));
+    MOSAIC_RC(linefill::finish(G, c, n_groups, recs.data(), seg_start.data(), useg.data(), items.data(), cells_only, cs.get(), &bad));
     if (bad >= 0) return linefill::fail_bad_cell(c, bad);
     *out = cs.release();
     return MOSAIC_OK;

@@ -25,25 +25,16 @@
 //               locations of step 4 go over the lanes the same way.
 //   k_lj_groups packs the occupied slots of the group hash; the host copies them back and sorts them by
 //               key pair.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
 #include <atomic>
 #include <memory>
-#include <string>
 #include <utility>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
 #include "chips_view.h"
-#include "geoms_device.h"
+#include "dev_rt.h"
 #include "line_chips_build.h"
 #include "line_isect.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
 
 struct mosaic_line_chips {
     int grid = 0, res = 0, device = 0;
@@ -67,20 +58,8 @@ namespace {
 constexpr int kBlock = 256;
 const unsigned long long kEmptyGroup = ~0ULL;
 
-#define LJ_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define LJ_HIP(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t _e = (expr);                                                                                  \
-        if (_e != hipSuccess)                                                                                    \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                   \
-                                    (std::string("line join: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
+using dev::blocks_for;
+using dev::Buf;
 
 struct PairRec {
     uint32_t line, poly, group;
@@ -290,25 +269,15 @@ __global__ void __launch_bounds__(kBlock) k_lj_groups(const unsigned long long* 
 
 template <class T>
 int upload(T** dst, const std::vector<T>& src, int64_t* bytes) {
-    LJ_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
-    if (!src.empty()) LJ_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    MOSAIC_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
+    if (!src.empty()) MOSAIC_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     *bytes += (int64_t)(src.size() * sizeof(T));
     return MOSAIC_OK;
 }
 
-int64_t blocks_for(int64_t n, int64_t cap) { return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
-
 std::atomic<int> g_team{64};
 thread_local int64_t t_last[4] = {0, 0, 0, 0};
 thread_local double t_ms[2] = {0, 0};
-
-struct Events {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 }  // namespace
 
@@ -320,9 +289,8 @@ int mosaic_line_chips_create(mosaic_ctx* ctx, int grid, int res, int64_t n_chips
     if (!ctx || !out) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
     if (grid != MOSAIC_GRID_H3 && grid != MOSAIC_GRID_BNG) return mosaic_tess_fail(MOSAIC_E_ARG, "unknown grid");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    LJ_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
     LineChipBuilder b;
     std::string err;
     if (int rc = build_line_chips(n_chips, is_core, index_id, key, wkb_offsets, offsets32, wkb, b, err))
@@ -332,17 +300,17 @@ int mosaic_line_chips_create(mosaic_ctx* ctx, int grid, int res, int64_t n_chips
     std::unique_ptr<mosaic_line_chips> t(new mosaic_line_chips());
     t->grid = grid;
     t->res = res;
-    t->device = device;
+    t->device = ex.device;
     t->n_chips = n_chips;
     t->n_pieces = (int64_t)b.piece_bbox.size();
     t->n_vertices = (int64_t)b.verts.size();
-    LJ_RC(upload(&t->verts, b.verts, &t->device_bytes));
-    LJ_RC(upload(&t->piece_start, b.piece_start, &t->device_bytes));
-    LJ_RC(upload(&t->piece_bbox, b.piece_bbox, &t->device_bytes));
-    LJ_RC(upload(&t->chip_piece, b.chip_piece, &t->device_bytes));
-    LJ_RC(upload(&t->chip_bbox, b.chip_bbox, &t->device_bytes));
-    LJ_RC(upload(&t->cell, b.cell, &t->device_bytes));
-    LJ_RC(upload(&t->meta, meta, &t->device_bytes));
+    MOSAIC_RC(upload(&t->verts, b.verts, &t->device_bytes));
+    MOSAIC_RC(upload(&t->piece_start, b.piece_start, &t->device_bytes));
+    MOSAIC_RC(upload(&t->piece_bbox, b.piece_bbox, &t->device_bytes));
+    MOSAIC_RC(upload(&t->chip_piece, b.chip_piece, &t->device_bytes));
+    MOSAIC_RC(upload(&t->chip_bbox, b.chip_bbox, &t->device_bytes));
+    MOSAIC_RC(upload(&t->cell, b.cell, &t->device_bytes));
+    MOSAIC_RC(upload(&t->meta, meta, &t->device_bytes));
     *out = t.release();
     return MOSAIC_OK;
 }
@@ -397,28 +365,27 @@ int mosaic_line_intersects_aggregate(mosaic_ctx* ctx, const mosaic_line_chips* l
         return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *n_out = 0;
     ChipsJoinView pv;
-    LJ_RC(mosaic_chips_join_view(polygons, &pv));
+    MOSAIC_RC(mosaic_chips_join_view(polygons, &pv));
     if (lines->grid != pv.grid || lines->res != pv.res)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersects_aggregate: both chip tables must use the same grid and resolution");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    LJ_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    if (lines->device != device || pv.device != device)
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    if (lines->device != ex.device || pv.device != ex.device)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersects_aggregate: a chip table of another device");
     std::fill(t_last, t_last + 4, 0);
     t_ms[0] = t_ms[1] = 0;
     if (lines->n_chips == 0 || pv.n_chips == 0 || pv.capacity == 0) return MOSAIC_OK;
-    hipStream_t stream = (hipStream_t)stream_v;
+    hipStream_t stream = ex.stream;
     const int64_t n = lines->n_chips;
-    const int64_t wide = (int64_t)n_cu * 16;
+    const int64_t wide = (int64_t)ex.n_cu * 16;
 
-    Events ev;
-    for (hipEvent_t& x : ev.e) LJ_HIP(hipEventCreate(&x));
-    DevMem s_counts, s_ovf, s_gkey, s_gflag, s_list, s_okey, s_oflag;
-    LJ_HIP(s_counts.alloc(6 * sizeof(unsigned long long)));
-    LJ_HIP(s_ovf.alloc(sizeof(int)));
-    LJ_HIP(hipMemsetAsync(s_counts.p, 0, 6 * sizeof(unsigned long long), stream));
-    LJ_HIP(hipMemsetAsync(s_ovf.p, 0, sizeof(int), stream));
+    dev::Events<5> ev;
+    MOSAIC_RC(ev.create());
+    Buf s_counts, s_ovf, s_gkey, s_gflag, s_list, s_okey, s_oflag;
+    MOSAIC_RC(s_counts.reserve(6 * sizeof(unsigned long long)));
+    MOSAIC_RC(s_ovf.reserve(sizeof(int)));
+    MOSAIC_HIP(hipMemsetAsync(s_counts.p, 0, 6 * sizeof(unsigned long long), stream));
+    MOSAIC_HIP(hipMemsetAsync(s_ovf.p, 0, sizeof(int), stream));
     ProbeArgs pa{};
     pa.cell = lines->cell;
     pa.meta = lines->meta;
@@ -429,34 +396,34 @@ int mosaic_line_intersects_aggregate(mosaic_ctx* ctx, const mosaic_line_chips* l
     pa.pass = 0;
     pa.counts = s_counts.as<unsigned long long>();
     pa.overflow = s_ovf.as<int>();
-    const dim3 pgrid((unsigned)blocks_for(n, wide));
-    LJ_HIP(hipEventRecord(ev.e[0], stream));
+    const dim3 pgrid((unsigned)blocks_for(n, kBlock, wide));
+    MOSAIC_HIP(hipEventRecord(ev.e[0], stream));
     hipLaunchKernelGGL(k_lj_probe, pgrid, dim3(kBlock), 0, stream, pa);
-    LJ_HIP(hipGetLastError());
-    LJ_HIP(hipEventRecord(ev.e[1], stream));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipEventRecord(ev.e[1], stream));
     unsigned long long counts[6] = {0, 0, 0, 0, 0, 0};
-    LJ_HIP(hipMemcpyAsync(counts, s_counts.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    LJ_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     const unsigned long long pairs = counts[0], plain = counts[1];
     if (pairs == 0) return MOSAIC_OK;
     if (pairs >= (1ull << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "st_intersects_aggregate (lines): 2^31 chip pairs or more");
     uint64_t gcap = 1024;
     while (gcap < 2 * pairs) gcap <<= 1;
-    LJ_HIP(s_gkey.alloc(gcap * 8));
-    LJ_HIP(s_gflag.alloc(gcap * 4));
-    LJ_HIP(s_list.alloc((size_t)plain * sizeof(PairRec)));
-    LJ_HIP(hipMemsetAsync(s_gkey.p, 0xff, gcap * 8, stream));
-    LJ_HIP(hipMemsetAsync(s_gflag.p, 0, gcap * 4, stream));
+    MOSAIC_RC(s_gkey.reserve(gcap * 8));
+    MOSAIC_RC(s_gflag.reserve(gcap * 4));
+    MOSAIC_RC(s_list.reserve((size_t)plain * sizeof(PairRec)));
+    MOSAIC_HIP(hipMemsetAsync(s_gkey.p, 0xff, gcap * 8, stream));
+    MOSAIC_HIP(hipMemsetAsync(s_gflag.p, 0, gcap * 4, stream));
     pa.pass = 1;
     pa.gkey = s_gkey.as<unsigned long long>();
     pa.gflag = s_gflag.as<uint32_t>();
     pa.gmask = gcap - 1;
     pa.list = s_list.as<PairRec>();
     pa.list_cap = plain;
-    LJ_HIP(hipEventRecord(ev.e[2], stream));
+    MOSAIC_HIP(hipEventRecord(ev.e[2], stream));
     hipLaunchKernelGGL(k_lj_probe, pgrid, dim3(kBlock), 0, stream, pa);
-    LJ_HIP(hipGetLastError());
-    LJ_HIP(hipEventRecord(ev.e[3], stream));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipEventRecord(ev.e[3], stream));
     if (plain) {
         // the list length is the count of pass 0 (the same enumeration), so it is known before pass 1 ends
         TestArgs ta{lineisect::LineStore{lines->verts, lines->piece_start, lines->piece_bbox, lines->chip_piece, lines->chip_bbox},
@@ -467,33 +434,33 @@ int mosaic_line_intersects_aggregate(mosaic_ctx* ctx, const mosaic_line_chips* l
             hipLaunchKernelGGL(k_lj_test<16>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ta);
         else
             hipLaunchKernelGGL(k_lj_test<64>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ta);
-        LJ_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    LJ_HIP(hipEventRecord(ev.e[4], stream));
+    MOSAIC_HIP(hipEventRecord(ev.e[4], stream));
     // the groups are at most the chip pairs: the occupied slots are packed on the device and only they come back
-    LJ_HIP(s_okey.alloc((size_t)pairs * 8));
-    LJ_HIP(s_oflag.alloc((size_t)pairs));
-    hipLaunchKernelGGL(k_lj_groups, dim3((unsigned)blocks_for((int64_t)gcap, wide)), dim3(kBlock), 0, stream, pa.gkey, pa.gflag, gcap,
+    MOSAIC_RC(s_okey.reserve((size_t)pairs * 8));
+    MOSAIC_RC(s_oflag.reserve((size_t)pairs));
+    hipLaunchKernelGGL(k_lj_groups, dim3((unsigned)blocks_for((int64_t)gcap, kBlock, wide)), dim3(kBlock), 0, stream, pa.gkey, pa.gflag, gcap,
                        s_okey.as<unsigned long long>(), s_oflag.as<uint8_t>(), pairs, pa.counts + 5);
-    LJ_HIP(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     int hov = 0;
-    LJ_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    LJ_HIP(hipMemcpyAsync(&hov, s_ovf.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    LJ_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipMemcpyAsync(&hov, s_ovf.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     if (hov || counts[2] != plain || counts[5] > pairs)
         return mosaic_tess_fail(MOSAIC_E_CAPACITY, "st_intersects_aggregate (lines): group table overflow");
     const size_t n_groups = (size_t)counts[5];
     std::vector<unsigned long long> hk(n_groups);
     std::vector<uint8_t> hf(n_groups);
     if (n_groups) {
-        LJ_HIP(hipMemcpyAsync(hk.data(), s_okey.p, n_groups * 8, hipMemcpyDeviceToHost, stream));
-        LJ_HIP(hipMemcpyAsync(hf.data(), s_oflag.p, n_groups, hipMemcpyDeviceToHost, stream));
-        LJ_HIP(hipStreamSynchronize(stream));
+        MOSAIC_HIP(hipMemcpyAsync(hk.data(), s_okey.p, n_groups * 8, hipMemcpyDeviceToHost, stream));
+        MOSAIC_HIP(hipMemcpyAsync(hf.data(), s_oflag.p, n_groups, hipMemcpyDeviceToHost, stream));
+        MOSAIC_HIP(hipStreamSynchronize(stream));
     }
     float m01 = 0, m23 = 0, m34 = 0;
-    LJ_HIP(hipEventElapsedTime(&m01, ev.e[0], ev.e[1]));
-    LJ_HIP(hipEventElapsedTime(&m23, ev.e[2], ev.e[3]));
-    LJ_HIP(hipEventElapsedTime(&m34, ev.e[3], ev.e[4]));
+    MOSAIC_HIP(hipEventElapsedTime(&m01, ev.e[0], ev.e[1]));
+    MOSAIC_HIP(hipEventElapsedTime(&m23, ev.e[2], ev.e[3]));
+    MOSAIC_HIP(hipEventElapsedTime(&m34, ev.e[3], ev.e[4]));
     std::vector<std::pair<unsigned long long, uint8_t>> groups(n_groups);
     for (size_t s = 0; s < n_groups; s++) groups[s] = {hk[s], hf[s]};
     std::sort(groups.begin(), groups.end());

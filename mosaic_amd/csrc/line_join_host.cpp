@@ -14,13 +14,12 @@
 #include <vector>
 
 #include "../../include/mosaic_hip.h"
+#include "fail.h"
 #include "geom_build.h"
 #include "line_chips_build.h"
 #include "line_isect.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
 
 namespace {
 

@@ -12,9 +12,8 @@
 
 #include "../../include/mosaic_hip.h"
 #include "chip_set.h"
+#include "fail.h"
 #include "line_fill.h"
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);  // defined in mosaic_hip.hip
 
 namespace mosaic {
 namespace linefill {

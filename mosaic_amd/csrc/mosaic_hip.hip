@@ -34,6 +34,7 @@
 #include "../../include/mosaic_hip.h"
 #include "bng_device.h"
 #include "chips_view.h"
+#include "dev_rt.h"
 #include "geom_build.h"
 #include "h3_device.h"
 #include "h3_geom.h"
@@ -75,11 +76,7 @@ static int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(MOSAIC_E_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
-    } while (0)
+#define HIP_TRY(expr) MOSAIC_HIP(expr)
 
 #include "join_chips.h"
 
@@ -1974,13 +1971,6 @@ struct DevBufGuard {
         for (DevBuf* b : bufs) b->release();
     }
 };
-struct EventGuard {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventGuard() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 // Options of a context (mosaic_set_option).  Every call copies them once at entry, so a call runs
 // with one consistent set even while another thread changes them.
@@ -2344,16 +2334,7 @@ struct mosaic_chips {
     }
 };
 
-// pointer residency: returns true if p is device-accessible memory of the current device
-static bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
+using dev::is_device_ptr;  // pointer residency: true if p is device-accessible memory of the current device
 
 // Make `src` (n_bytes) available on the device: returns the pointer to use.
 static int to_device(ThreadCtx* c, DevBuf& stage, const void* src, size_t n_bytes, const void** out) {
@@ -5669,7 +5650,7 @@ int mosaic_tess_classify_bng(mosaic_ctx* ctx, int64_t n_geoms, const int64_t* ge
     a.eps = eps;
     a.cls = (uint8_t*)s_cls.p;
     const int64_t blocks = std::min<int64_t>((n_cand + 3) / 4, (int64_t)c->n_cu * 16);  // 4 waves per block
-    EventGuard ev;
+    dev::Events<2> ev;
     HIP_TRY(hipEventCreate(&ev.e[0]));
     HIP_TRY(hipEventCreate(&ev.e[1]));
     hipEvent_t t0 = ev.e[0], t1 = ev.e[1];
@@ -5914,7 +5895,7 @@ static int run_clip_ll(ThreadCtx* c, ClipLLBufs& B, const void* d_gxy, const voi
     a.blk = ri ? (const double*)ri->blk.p : nullptr;
     a.ring_blk = ri ? (const int64_t*)ri->rblk.p : nullptr;
     a.ring_ccw = ri ? (const uint8_t*)ri->ccw.p : nullptr;
-    EventGuard ev;
+    dev::Events<2> ev;
     HIP_TRY(hipEventCreate(&ev.e[0]));
     HIP_TRY(hipEventCreate(&ev.e[1]));
     HIP_TRY(hipEventRecord(ev.e[0], c->stream));
@@ -6120,7 +6101,7 @@ int tessclip::h3_session_chunk(H3Session* S, int64_t nc, const int32_t* cand_geo
     ca.eps = eps;
     ca.cls = (uint8_t*)S->d_cls.p;
     const int64_t blocks = std::min<int64_t>((nc + 3) / 4, (int64_t)c->n_cu * 16);
-    EventGuard ev;
+    dev::Events<2> ev;
     HIP_TRY(hipEventCreate(&ev.e[0]));
     HIP_TRY(hipEventCreate(&ev.e[1]));
     HIP_TRY(hipEventRecord(ev.e[0], c->stream));
@@ -6206,7 +6187,7 @@ int mosaic_tess_classify_poly(mosaic_ctx* ctx, int64_t n_geoms, const int64_t* g
     a.eps = eps;
     a.cls = (uint8_t*)s_cls.p;
     const int64_t blocks = std::min<int64_t>((n_cand + 3) / 4, (int64_t)c->n_cu * 16);
-    EventGuard ev;
+    dev::Events<2> ev;
     HIP_TRY(hipEventCreate(&ev.e[0]));
     HIP_TRY(hipEventCreate(&ev.e[1]));
     hipEvent_t t0 = ev.e[0], t1 = ev.e[1];

@@ -1,10 +1,8 @@
 // What the pair kernels over geometry columns share (st_distance.hip, st_intersects.hip): the device
-// view of a column, the per-wave append to a work list, and the grid size of a one-lane-per-item kernel.
+// view of a column, the per-wave append to a work list, and the block size of their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <algorithm>
 
 #include "geoms_device.h"
 #include "pip_device.h"
@@ -37,10 +35,6 @@ __device__ inline unsigned long long wave_append(unsigned long long* counter, bo
     if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
     base = (unsigned long long)__shfl((long long)base, leader, 64);
     return base + (unsigned long long)__popcll(m & (((unsigned long long)1 << lane) - 1));
-}
-
-inline int64_t blocks_for(int64_t n, int64_t cap) {
-    return std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap));
 }
 
 }  // namespace pairs

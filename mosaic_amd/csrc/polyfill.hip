@@ -27,28 +27,18 @@
 // 2.12 immutable HashSet iterates them (hash-trie order of the improved Long hash) when there are
 // more than four (Set1..Set4 keep insertion order, which is not restated: such rows are ordered
 // the same way).
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <stdint.h>
-
-#include <algorithm>
 #include <cmath>
 #include <memory>
-#include <string>
 #include <unordered_set>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
 #include "bng_device.h"
 #include "cell_lists.h"
+#include "dev_rt.h"
 #include "h3_grid.h"
 #include "h3_polyfill.h"
 #include "pip_device.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_exec(mosaic_ctx* ctx, int* device, void** stream, int* jdk, int* n_cu);
 
 namespace {
 
@@ -312,46 +302,9 @@ __global__ void __launch_bounds__(256) k_pf_bng_round(BngArgs a, const uint64_t*
 }
 
 // ---- host helpers ----
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    int reserve(size_t n) {
-        if (n <= bytes) return MOSAIC_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        if (hipMalloc(&p, std::max<size_t>(n, 8)) != hipSuccess)
-            return mosaic_tess_fail(MOSAIC_E_NOMEM, ("hipMalloc(" + std::to_string(n) + ") failed").c_str());
-        bytes = std::max<size_t>(n, 8);
-        return MOSAIC_OK;
-    }
-    template <class T>
-    T* as() const {
-        return (T*)p;
-    }
-};
-
-#define PF_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            return mosaic_tess_fail(MOSAIC_E_HIP, (std::string(#expr ": ") + hipGetErrorString(_e)).c_str()); \
-    } while (0)
-#define PF_RC(expr)              \
-    do {                         \
-        int _rc = (expr);        \
-        if (_rc) return _rc;     \
-    } while (0)
-
-template <class T>
-int upload(Buf& b, const std::vector<T>& v, hipStream_t s) {
-    PF_RC(b.reserve(v.size() * sizeof(T)));
-    if (!v.empty()) PF_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return MOSAIC_OK;
-}
+using dev::blocks_for;
+using dev::Buf;
+using dev::upload;
 
 uint64_t pow2_at_least(uint64_t n) {
     uint64_t c = 1024;
@@ -359,18 +312,16 @@ uint64_t pow2_at_least(uint64_t n) {
     return c;
 }
 
-int blocks_for(int64_t n, int n_cu) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)n_cu * 16)); }
-
 // Compacts the non-empty keys of in[0, n) into out (order kept); returns the count through *count.
 int compact(Buf& tmp, const uint64_t* in, int64_t n, uint64_t* out, Buf& count_buf, int64_t* count, hipStream_t s) {
-    PF_RC(count_buf.reserve(8));
+    MOSAIC_RC(count_buf.reserve(8));
     size_t bytes = 0;
-    PF_TRY(hipcub::DeviceSelect::If(nullptr, bytes, in, out, count_buf.as<int64_t>(), n, NotEmpty(), s));
-    PF_RC(tmp.reserve(bytes));
+    MOSAIC_HIP(hipcub::DeviceSelect::If(nullptr, bytes, in, out, count_buf.as<int64_t>(), n, NotEmpty(), s));
+    MOSAIC_RC(tmp.reserve(bytes));
     bytes = tmp.bytes;
-    PF_TRY(hipcub::DeviceSelect::If(tmp.p, bytes, in, out, count_buf.as<int64_t>(), n, NotEmpty(), s));
-    PF_TRY(hipMemcpyAsync(count, count_buf.p, 8, hipMemcpyDeviceToHost, s));
-    PF_TRY(hipStreamSynchronize(s));
+    MOSAIC_HIP(hipcub::DeviceSelect::If(tmp.p, bytes, in, out, count_buf.as<int64_t>(), n, NotEmpty(), s));
+    MOSAIC_HIP(hipMemcpyAsync(count, count_buf.p, 8, hipMemcpyDeviceToHost, s));
+    MOSAIC_HIP(hipStreamSynchronize(s));
     return MOSAIC_OK;
 }
 
@@ -550,33 +501,33 @@ int h3_batch(hipStream_t st, int n_cu, int jdk, int res, const Input& in, int64_
     double pent_r = 0;
     {
         Buf d_sb, d_tot, d_m, d_pr;
-        PF_RC(upload(d_sb, shell_box, st));
-        PF_RC(upload(d_tot, part_total, st));
-        PF_RC(d_m.reserve((size_t)np * 8));
-        PF_RC(d_pr.reserve(8));
-        hipLaunchKernelGGL(k_pf_part_m, dim3(blocks_for(np, n_cu)), dim3(256), 0, st, d_sb.as<h3fill::Box>(),
+        MOSAIC_RC(upload(d_sb, shell_box, st));
+        MOSAIC_RC(upload(d_tot, part_total, st));
+        MOSAIC_RC(d_m.reserve((size_t)np * 8));
+        MOSAIC_RC(d_pr.reserve(8));
+        hipLaunchKernelGGL(k_pf_part_m, dim3(blocks_for(np, 256, n_cu * 16)), dim3(256), 0, st, d_sb.as<h3fill::Box>(),
                            d_tot.as<int64_t>(), np, res, d_m.as<int64_t>(), d_pr.as<double>());
-        PF_TRY(hipGetLastError());
-        PF_TRY(hipMemcpyAsync(part_m.data(), d_m.p, (size_t)np * 8, hipMemcpyDeviceToHost, st));
-        PF_TRY(hipMemcpyAsync(&pent_r, d_pr.p, 8, hipMemcpyDeviceToHost, st));
-        PF_TRY(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipGetLastError());
+        MOSAIC_HIP(hipMemcpyAsync(part_m.data(), d_m.p, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(&pent_r, d_pr.p, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
     }
     uint64_t m_sum = 0;
     for (int64_t m : part_m) m_sum += (uint64_t)m;
     Buf d_lat, d_lon, d_roff, d_vring, d_rpart, d_pring, d_box, d_en, d_soff, d_flags, d_fail, d_tmp, d_cnt;
-    PF_RC(upload(d_lat, lat, st));
-    PF_RC(upload(d_lon, lon, st));
-    PF_RC(upload(d_roff, ring_off, st));
-    PF_RC(upload(d_vring, v_ring, st));
-    PF_RC(upload(d_rpart, ring_part, st));
-    PF_RC(upload(d_pring, part_ring, st));
-    PF_RC(upload(d_box, boxes, st));
-    PF_RC(d_en.reserve((size_t)nv * 8));
-    PF_RC(d_soff.reserve((size_t)(nv + 1) * 8));
-    PF_RC(d_flags.reserve(4));
-    PF_RC(d_fail.reserve((size_t)np * 4));
-    PF_TRY(hipMemsetAsync(d_flags.p, 0, 4, st));
-    PF_TRY(hipMemsetAsync(d_fail.p, 0, (size_t)np * 4, st));
+    MOSAIC_RC(upload(d_lat, lat, st));
+    MOSAIC_RC(upload(d_lon, lon, st));
+    MOSAIC_RC(upload(d_roff, ring_off, st));
+    MOSAIC_RC(upload(d_vring, v_ring, st));
+    MOSAIC_RC(upload(d_rpart, ring_part, st));
+    MOSAIC_RC(upload(d_pring, part_ring, st));
+    MOSAIC_RC(upload(d_box, boxes, st));
+    MOSAIC_RC(d_en.reserve((size_t)nv * 8));
+    MOSAIC_RC(d_soff.reserve((size_t)(nv + 1) * 8));
+    MOSAIC_RC(d_flags.reserve(4));
+    MOSAIC_RC(d_fail.reserve((size_t)np * 4));
+    MOSAIC_HIP(hipMemsetAsync(d_flags.p, 0, 4, st));
+    MOSAIC_HIP(hipMemsetAsync(d_fail.p, 0, (size_t)np * 4, st));
     H3Args a{};
     a.lat = d_lat.as<double>();
     a.lon = d_lon.as<double>();
@@ -592,104 +543,91 @@ int h3_batch(hipStream_t st, int n_cu, int jdk, int res, const Input& in, int64_
     a.sample_off = d_soff.as<int64_t>();
     a.flags = d_flags.as<unsigned int>();
     a.part_fail = d_fail.as<int32_t>();
-    hipEvent_t e0, e1;
-    PF_TRY(hipEventCreate(&e0));
-    PF_TRY(hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
-        ~EvGuard() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-        }
-    } evg{e0, e1};
-    PF_TRY(hipEventRecord(e0, st));
+    dev::Events<2> ev;
+    MOSAIC_RC(ev.create());
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
+    MOSAIC_HIP(hipEventRecord(e0, st));
     // 1. edge samples -> first frontier
-    hipLaunchKernelGGL(k_pf_edge_count, dim3(blocks_for(nv, n_cu)), dim3(256), 0, st, a);
-    PF_TRY(hipGetLastError());
-    PF_TRY(hipMemsetAsync(a.sample_off, 0, 8, st));
-    {
-        size_t bytes = 0;
-        PF_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, a.edge_n, a.sample_off + 1, nv, st));
-        PF_RC(d_tmp.reserve(bytes));
-        bytes = d_tmp.bytes;
-        PF_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp.p, bytes, a.edge_n, a.sample_off + 1, nv, st));
-    }
+    hipLaunchKernelGGL(k_pf_edge_count, dim3(blocks_for(nv, 256, n_cu * 16)), dim3(256), 0, st, a);
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemsetAsync(a.sample_off, 0, 8, st));
+    MOSAIC_RC(dev::inclusive_sum(d_tmp, a.edge_n, a.sample_off + 1, nv, st));
     int64_t n_samples = 0;
-    PF_TRY(hipMemcpyAsync(&n_samples, a.sample_off + nv, 8, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(&n_samples, a.sample_off + nv, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     if (n_samples >= ((int64_t)1 << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "polyfill: too many edge samples");
     Buf d_skey, d_sslot, d_tkeys, d_tval, d_keep, d_front, d_nb, d_nslot, d_okeys, d_result;
-    PF_RC(d_skey.reserve((size_t)n_samples * 8));
-    PF_RC(d_sslot.reserve((size_t)n_samples * 8));
-    PF_RC(d_keep.reserve((size_t)n_samples * 8));
-    PF_RC(d_front.reserve((size_t)n_samples * 8));
+    MOSAIC_RC(d_skey.reserve((size_t)n_samples * 8));
+    MOSAIC_RC(d_sslot.reserve((size_t)n_samples * 8));
+    MOSAIC_RC(d_keep.reserve((size_t)n_samples * 8));
+    MOSAIC_RC(d_front.reserve((size_t)n_samples * 8));
     uint64_t tcap = pow2_at_least(2 * (uint64_t)n_samples);
-    PF_RC(d_tkeys.reserve(tcap * 8));
-    PF_RC(d_tval.reserve(tcap * 4));
-    PF_TRY(hipMemsetAsync(d_tkeys.p, 0xff, tcap * 8, st));
-    PF_TRY(hipMemsetAsync(d_tval.p, 0xff, tcap * 4, st));
+    MOSAIC_RC(d_tkeys.reserve(tcap * 8));
+    MOSAIC_RC(d_tval.reserve(tcap * 4));
+    MOSAIC_HIP(hipMemsetAsync(d_tkeys.p, 0xff, tcap * 8, st));
+    MOSAIC_HIP(hipMemsetAsync(d_tval.p, 0xff, tcap * 4, st));
     a.s_key = d_skey.as<uint64_t>();
     a.s_slot = d_sslot.as<uint64_t>();
     a.tab_keys = d_tkeys.as<uint64_t>();
     a.tab_val = d_tval.as<uint32_t>();
     a.tab_mask = tcap - 1;
-    hipLaunchKernelGGL(k_pf_edge_sample, dim3(blocks_for(n_samples, n_cu)), dim3(256), 0, st, a, n_samples);
-    PF_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pf_edge_first, dim3(blocks_for(n_samples, n_cu)), dim3(256), 0, st, a, n_samples,
+    hipLaunchKernelGGL(k_pf_edge_sample, dim3(blocks_for(n_samples, 256, n_cu * 16)), dim3(256), 0, st, a, n_samples);
+    MOSAIC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pf_edge_first, dim3(blocks_for(n_samples, 256, n_cu * 16)), dim3(256), 0, st, a, n_samples,
                        d_keep.as<uint64_t>());
-    PF_TRY(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     int64_t f = 0;
-    PF_RC(compact(d_tmp, d_keep.as<uint64_t>(), n_samples, d_front.as<uint64_t>(), d_cnt, &f, st));
+    MOSAIC_RC(compact(d_tmp, d_keep.as<uint64_t>(), n_samples, d_front.as<uint64_t>(), d_cnt, &f, st));
     // 2. breadth-first rounds
     const uint64_t ocap = pow2_at_least(2 * m_sum);
     if (ocap > ((uint64_t)1 << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "polyfill: result too large for one call");
-    PF_RC(d_okeys.reserve(ocap * 8));
-    PF_TRY(hipMemsetAsync(d_okeys.p, 0xff, ocap * 8, st));
-    PF_RC(d_result.reserve(m_sum * 8));
+    MOSAIC_RC(d_okeys.reserve(ocap * 8));
+    MOSAIC_HIP(hipMemsetAsync(d_okeys.p, 0xff, ocap * 8, st));
+    MOSAIC_RC(d_result.reserve(m_sum * 8));
     a.out_keys = d_okeys.as<uint64_t>();
     a.out_mask = ocap - 1;
     int64_t r_total = 0;
     while (f > 0) {
         const int64_t m = 7 * f;
-        PF_RC(d_nb.reserve((size_t)m * 8));
-        PF_RC(d_nslot.reserve((size_t)m * 8));
-        if (d_keep.bytes < (size_t)m * 8) PF_RC(d_keep.reserve((size_t)m * 8));
+        MOSAIC_RC(d_nb.reserve((size_t)m * 8));
+        MOSAIC_RC(d_nslot.reserve((size_t)m * 8));
+        if (d_keep.bytes < (size_t)m * 8) MOSAIC_RC(d_keep.reserve((size_t)m * 8));
         const uint64_t need = pow2_at_least(2 * (uint64_t)m);
         if (need > tcap) {
             tcap = need;
-            PF_RC(d_tkeys.reserve(tcap * 8));
-            PF_RC(d_tval.reserve(tcap * 4));
+            MOSAIC_RC(d_tkeys.reserve(tcap * 8));
+            MOSAIC_RC(d_tval.reserve(tcap * 4));
         }
         a.tab_keys = d_tkeys.as<uint64_t>();
         a.tab_val = d_tval.as<uint32_t>();
         a.tab_mask = need - 1;
-        PF_TRY(hipMemsetAsync(d_tkeys.p, 0xff, need * 8, st));
-        PF_TRY(hipMemsetAsync(d_tval.p, 0xff, need * 4, st));
-        hipLaunchKernelGGL(k_pf_expand, dim3(blocks_for(f, n_cu)), dim3(256), 0, st, a, d_front.as<uint64_t>(), f,
+        MOSAIC_HIP(hipMemsetAsync(d_tkeys.p, 0xff, need * 8, st));
+        MOSAIC_HIP(hipMemsetAsync(d_tval.p, 0xff, need * 4, st));
+        hipLaunchKernelGGL(k_pf_expand, dim3(blocks_for(f, 256, n_cu * 16)), dim3(256), 0, st, a, d_front.as<uint64_t>(), f,
                            d_nb.as<uint64_t>(), d_nslot.as<uint64_t>());
-        PF_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_pf_accept, dim3(blocks_for(m, n_cu)), dim3(256), 0, st, a, d_nb.as<uint64_t>(),
+        MOSAIC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pf_accept, dim3(blocks_for(m, 256, n_cu * 16)), dim3(256), 0, st, a, d_nb.as<uint64_t>(),
                            d_nslot.as<uint64_t>(), m, d_keep.as<uint64_t>());
-        PF_TRY(hipGetLastError());
-        if (d_front.bytes < (size_t)m * 8) PF_RC(d_front.reserve((size_t)m * 8));
-        PF_RC(compact(d_tmp, d_keep.as<uint64_t>(), m, d_front.as<uint64_t>(), d_cnt, &f, st));
+        MOSAIC_HIP(hipGetLastError());
+        if (d_front.bytes < (size_t)m * 8) MOSAIC_RC(d_front.reserve((size_t)m * 8));
+        MOSAIC_RC(compact(d_tmp, d_keep.as<uint64_t>(), m, d_front.as<uint64_t>(), d_cnt, &f, st));
         if (f > 0) {
-            hipLaunchKernelGGL(k_pf_commit, dim3(blocks_for(f, n_cu)), dim3(256), 0, st, a, d_front.as<uint64_t>(), f,
+            hipLaunchKernelGGL(k_pf_commit, dim3(blocks_for(f, 256, n_cu * 16)), dim3(256), 0, st, a, d_front.as<uint64_t>(), f,
                                d_result.as<uint64_t>(), r_total, (int64_t)m_sum);
-            PF_TRY(hipGetLastError());
+            MOSAIC_HIP(hipGetLastError());
         }
         r_total += f;
         if (r_total > (int64_t)m_sum) break;
     }
-    PF_TRY(hipEventRecord(e1, st));
+    MOSAIC_HIP(hipEventRecord(e1, st));
     unsigned int flags = 0;
     std::vector<int32_t> fails(np);
     std::vector<uint64_t> result((size_t)std::min<int64_t>(r_total, (int64_t)m_sum));
-    PF_TRY(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipMemcpyAsync(fails.data(), d_fail.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(fails.data(), d_fail.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
     if (!result.empty())
-        PF_TRY(hipMemcpyAsync(result.data(), d_result.p, result.size() * 8, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipMemcpyAsync(result.data(), d_result.p, result.size() * 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     *kernel_ms += ms;
@@ -784,24 +722,24 @@ int bng_batch(hipStream_t st, int n_cu, int res, const Input& in, int64_t g0, in
     const uint64_t vcap = pow2_at_least(2 * visit_bound);
     if (vcap > ((uint64_t)1 << 31)) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "polyfill: result too large for one call");
     Buf d_verts, d_rs, d_rb, d_pr, d_gp, d_gb, d_px, d_py, d_pg, d_vis, d_f0, d_f1, d_res, d_cnt, d_flags;
-    PF_RC(upload(d_verts, verts, st));
-    PF_RC(upload(d_rs, ring_start, st));
-    PF_RC(upload(d_rb, ring_box, st));
-    PF_RC(upload(d_pr, part_ring, st));
-    PF_RC(upload(d_gp, geom_part, st));
-    PF_RC(upload(d_gb, geom_box, st));
-    PF_RC(upload(d_px, px, st));
-    PF_RC(upload(d_py, py, st));
-    PF_RC(upload(d_pg, pg, st));
-    PF_RC(d_vis.reserve(vcap * 8));
-    PF_RC(d_f0.reserve(visit_bound * 8));
-    PF_RC(d_f1.reserve(visit_bound * 8));
-    PF_RC(d_res.reserve(visit_bound * 8));
-    PF_RC(d_cnt.reserve(16));
-    PF_RC(d_flags.reserve(4));
-    PF_TRY(hipMemsetAsync(d_vis.p, 0xff, vcap * 8, st));
-    PF_TRY(hipMemsetAsync(d_cnt.p, 0, 16, st));
-    PF_TRY(hipMemsetAsync(d_flags.p, 0, 4, st));
+    MOSAIC_RC(upload(d_verts, verts, st));
+    MOSAIC_RC(upload(d_rs, ring_start, st));
+    MOSAIC_RC(upload(d_rb, ring_box, st));
+    MOSAIC_RC(upload(d_pr, part_ring, st));
+    MOSAIC_RC(upload(d_gp, geom_part, st));
+    MOSAIC_RC(upload(d_gb, geom_box, st));
+    MOSAIC_RC(upload(d_px, px, st));
+    MOSAIC_RC(upload(d_py, py, st));
+    MOSAIC_RC(upload(d_pg, pg, st));
+    MOSAIC_RC(d_vis.reserve(vcap * 8));
+    MOSAIC_RC(d_f0.reserve(visit_bound * 8));
+    MOSAIC_RC(d_f1.reserve(visit_bound * 8));
+    MOSAIC_RC(d_res.reserve(visit_bound * 8));
+    MOSAIC_RC(d_cnt.reserve(16));
+    MOSAIC_RC(d_flags.reserve(4));
+    MOSAIC_HIP(hipMemsetAsync(d_vis.p, 0xff, vcap * 8, st));
+    MOSAIC_HIP(hipMemsetAsync(d_cnt.p, 0, 16, st));
+    MOSAIC_HIP(hipMemsetAsync(d_flags.p, 0, 4, st));
     BngArgs a{};
     a.store = pip::GeomStore{d_verts.as<pip::Vec2>(), d_rs.as<uint32_t>(), d_rb.as<pip::Box>(), d_pr.as<uint32_t>(),
                              d_gp.as<uint32_t>(), d_gb.as<pip::Box>()};
@@ -813,44 +751,37 @@ int bng_batch(hipStream_t st, int n_cu, int res, const Input& in, int64_t g0, in
     a.n_result = d_cnt.as<unsigned long long>() + 1;
     a.result_cap = (int64_t)visit_bound;
     a.flags = d_flags.as<unsigned int>();
-    hipEvent_t e0, e1;
-    PF_TRY(hipEventCreate(&e0));
-    PF_TRY(hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
-        ~EvGuard() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-        }
-    } evg{e0, e1};
-    PF_TRY(hipEventRecord(e0, st));
+    dev::Events<2> ev;
+    MOSAIC_RC(ev.create());
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
+    MOSAIC_HIP(hipEventRecord(e0, st));
     Buf* cur = &d_f0;
     Buf* nxt = &d_f1;
     a.next = cur->as<uint64_t>();
     a.n_next = d_cnt.as<unsigned long long>();
     const int64_t np = (int64_t)px.size();
-    hipLaunchKernelGGL(k_pf_bng_start, dim3(blocks_for(np, n_cu)), dim3(256), 0, st, a, d_px.as<double>(),
+    hipLaunchKernelGGL(k_pf_bng_start, dim3(blocks_for(np, 256, n_cu * 16)), dim3(256), 0, st, a, d_px.as<double>(),
                        d_py.as<double>(), d_pg.as<int32_t>(), np);
-    PF_TRY(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long f = 0;
-    PF_TRY(hipMemcpyAsync(&f, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(&f, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     while (f > 0 && (int64_t)f <= a.next_cap) {
-        PF_TRY(hipMemsetAsync(d_cnt.p, 0, 8, st));
+        MOSAIC_HIP(hipMemsetAsync(d_cnt.p, 0, 8, st));
         a.next = nxt->as<uint64_t>();
-        hipLaunchKernelGGL(k_pf_bng_round, dim3(blocks_for((int64_t)f, n_cu)), dim3(256), 0, st, a,
+        hipLaunchKernelGGL(k_pf_bng_round, dim3(blocks_for((int64_t)f, 256, n_cu * 16)), dim3(256), 0, st, a,
                            cur->as<uint64_t>(), (int64_t)f);
-        PF_TRY(hipGetLastError());
-        PF_TRY(hipMemcpyAsync(&f, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
-        PF_TRY(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipGetLastError());
+        MOSAIC_HIP(hipMemcpyAsync(&f, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
         std::swap(cur, nxt);
     }
-    PF_TRY(hipEventRecord(e1, st));
+    MOSAIC_HIP(hipEventRecord(e1, st));
     unsigned int flags = 0;
     unsigned long long n_res = 0;
-    PF_TRY(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipMemcpyAsync(&n_res, (char*)d_cnt.p + 8, 8, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(&flags, d_flags.p, 4, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipMemcpyAsync(&n_res, (char*)d_cnt.p + 8, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     *kernel_ms += ms;
@@ -858,7 +789,7 @@ int bng_batch(hipStream_t st, int n_cu, int res, const Input& in, int64_t g0, in
     if ((flags & 6u) || (int64_t)n_res > a.result_cap)
         return mosaic_tess_fail(MOSAIC_E_CAPACITY, "polyfill: device table overflow");
     std::vector<uint64_t> result((size_t)n_res);
-    if (n_res) PF_TRY(hipMemcpy(result.data(), d_res.p, (size_t)n_res * 8, hipMemcpyDeviceToHost));
+    if (n_res) MOSAIC_HIP(hipMemcpy(result.data(), d_res.p, (size_t)n_res * 8, hipMemcpyDeviceToHost));
     for (uint64_t k : result) cells[(size_t)(k >> kBngShift)].push_back((int64_t)(k & kBngLow));
     for (auto& v : cells) {
         std::vector<std::pair<uint64_t, int64_t>> o;
@@ -884,10 +815,9 @@ int mosaic_polyfill(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const i
     if (grid == MOSAIC_GRID_H3 ? (res < 0 || res > 15) : (grid == MOSAIC_GRID_BNG ? !bng::valid_resolution(res) : true))
         return mosaic_tess_fail(grid == MOSAIC_GRID_H3 || grid == MOSAIC_GRID_BNG ? MOSAIC_E_RES : MOSAIC_E_ARG,
                                 "invalid grid or resolution");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    PF_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
-    hipStream_t st = (hipStream_t)stream;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    hipStream_t st = ex.stream;
     const Input in{n_geoms, geom_parts, part_rings, ring_offsets, xy};
     std::unique_ptr<mosaic_cell_lists> lists(new mosaic_cell_lists());
     lists->status.assign((size_t)n_geoms, MOSAIC_POLYFILL_OK);
@@ -901,7 +831,7 @@ int mosaic_polyfill(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const i
             const int64_t e = std::min(n_parts, b + kBatch);
             std::vector<std::vector<int64_t>> pc((size_t)(e - b));
             std::vector<char> pb((size_t)(e - b), 0);
-            PF_RC(h3_batch(st, n_cu, jdk, res, in, pbase + b, pbase + e, pc, pb, &ms));
+            MOSAIC_RC(h3_batch(st, ex.n_cu, ex.jdk, res, in, pbase + b, pbase + e, pc, pb, &ms));
             for (int64_t q = b; q < e; q++) {
                 part_cells[q].swap(pc[q - b]);
                 part_bad[q] = pb[q - b];
@@ -923,7 +853,7 @@ int mosaic_polyfill(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const i
             const int64_t e = std::min(n_geoms, b + kBatch);
             std::vector<std::vector<int64_t>> gc((size_t)(e - b));
             std::vector<char> gb((size_t)(e - b), 0);
-            PF_RC(bng_batch(st, n_cu, res, in, b, e, gc, gb, &ms));
+            MOSAIC_RC(bng_batch(st, ex.n_cu, res, in, b, e, gc, gb, &ms));
             for (int64_t g = b; g < e; g++) {
                 if (gb[g - b]) lists->status[g] = MOSAIC_POLYFILL_UNSUPPORTED;
                 else lists->cells.insert(lists->cells.end(), gc[g - b].begin(), gc[g - b].end());
@@ -971,24 +901,23 @@ int mosaic_buffer_radius(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, co
     if (grid != MOSAIC_GRID_H3 || res < 0 || res > 15)
         return mosaic_tess_fail(grid == MOSAIC_GRID_H3 ? MOSAIC_E_RES : MOSAIC_E_ARG, "invalid grid or resolution");
     if (n_geoms == 0) return MOSAIC_OK;
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    PF_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
-    hipStream_t st = (hipStream_t)stream;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    hipStream_t st = ex.stream;
     std::vector<double> cx((size_t)n_geoms, 0), cy((size_t)n_geoms, 0);
     std::vector<uint8_t> ok((size_t)n_geoms, 0);
     for (int64_t g = 0; g < n_geoms; g++)
         ok[g] = jts_centroid(g, geom_parts, part_rings, ring_offsets, xy, &cx[g], &cy[g]) ? 1 : 0;
     Buf d_cx, d_cy, d_ok, d_out;
-    PF_RC(upload(d_cx, cx, st));
-    PF_RC(upload(d_cy, cy, st));
-    PF_RC(upload(d_ok, ok, st));
-    PF_RC(d_out.reserve((size_t)n_geoms * 8));
-    hipLaunchKernelGGL(k_buffer_radius_h3, dim3(blocks_for(n_geoms, n_cu)), dim3(256), 0, st, d_cx.as<double>(),
-                       d_cy.as<double>(), d_ok.as<uint8_t>(), n_geoms, res, jdk, d_out.as<double>());
-    PF_TRY(hipGetLastError());
-    PF_TRY(hipMemcpyAsync(out, d_out.p, (size_t)n_geoms * 8, hipMemcpyDeviceToHost, st));
-    PF_TRY(hipStreamSynchronize(st));
+    MOSAIC_RC(upload(d_cx, cx, st));
+    MOSAIC_RC(upload(d_cy, cy, st));
+    MOSAIC_RC(upload(d_ok, ok, st));
+    MOSAIC_RC(d_out.reserve((size_t)n_geoms * 8));
+    hipLaunchKernelGGL(k_buffer_radius_h3, dim3(blocks_for(n_geoms, 256, ex.n_cu * 16)), dim3(256), 0, st, d_cx.as<double>(),
+                       d_cy.as<double>(), d_ok.as<uint8_t>(), n_geoms, res, ex.jdk, d_out.as<double>());
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemcpyAsync(out, d_out.p, (size_t)n_geoms * 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     return MOSAIC_OK;
 }
 

@@ -25,22 +25,13 @@
 //
 // The reference's st_intersects_aggregate filter is a no-op in this join (ring_neighbours.h) and is
 // not built.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <stdint.h>
-
-#include <algorithm>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
+#include "dev_rt.h"
 #include "geoms_device.h"
 #include "ring_neighbours.h"
 
 using namespace mosaic;
-
-extern "C" int mosaic_tess_fail(int code, const char* msg);
 
 struct mosaic_cell_index {
     int device = 0;
@@ -71,22 +62,8 @@ namespace {
 
 constexpr int kBlock = 256;
 
-#define RN_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define RN_HIP(expr)                                                                                               \
-    do {                                                                                                           \
-        hipError_t _e = (expr);                                                                                    \
-        if (_e != hipSuccess)                                                                                      \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                     \
-                                    (std::string("ring_neighbours: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
-
-unsigned blocks_for(int64_t n, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, cap)); }
+using dev::blocks_for;
+using dev::Buf;
 
 int bits_for(int64_t n) {  // bits that hold every value below n
     int b = 1;
@@ -229,25 +206,6 @@ __global__ void __launch_bounds__(kBlock) k_rn_narrow(const uint32_t* in, int64_
         out[i] = in[i] ? 1 : 0;
 }
 
-template <class K, class V>
-int sort_pairs(const K* k_in, K* k_out, const V* v_in, V* v_out, int64_t n, int begin_bit, int end_bit, hipStream_t st) {
-    size_t bytes = 0;
-    RN_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k_in, k_out, v_in, v_out, (int)n, begin_bit, end_bit, st));
-    DevMem tmp;
-    RN_HIP(tmp.alloc(bytes));
-    RN_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, k_in, k_out, v_in, v_out, (int)n, begin_bit, end_bit, st));
-    RN_HIP(hipStreamSynchronize(st));  // tmp is freed on return
-    return MOSAIC_OK;
-}
-
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 thread_local double g_last_ms[3] = {0, 0, 0};
 
 }  // namespace
@@ -261,70 +219,66 @@ int mosaic_cell_index_create(mosaic_ctx* ctx, int64_t n_chips, const int64_t* in
     if (!ctx || !out || n_chips < 0 || (n_chips > 0 && (!index_id || !key))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
     if (n_chips >= rn::kMaxRows) return mosaic_tess_fail(MOSAIC_E_ARG, "cell index: 2^31 - 1 chips at the most");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    RN_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    hipStream_t st = (hipStream_t)stream_v;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    hipStream_t st = ex.stream;
     std::unique_ptr<mosaic_cell_index> ix(new mosaic_cell_index());
-    ix->device = device;
+    ix->device = ex.device;
     const int64_t n = n_chips;
     if (n == 0) {
-        RN_HIP(hipMalloc((void**)&ix->start, 16));
-        RN_HIP(hipMemsetAsync(ix->start, 0, 16, st));
-        RN_HIP(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipMalloc((void**)&ix->start, 16));
+        MOSAIC_HIP(hipMemsetAsync(ix->start, 0, 16, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
         *out = ix.release();
         return MOSAIC_OK;
     }
-    const int64_t wide = (int64_t)n_cu * 16;
-    DevMem s_id, s_key, d_counts, d_row0, d_row1, d_cell0, d_cell1, d_flags, d_tmp;
+    const int64_t wide = (int64_t)ex.n_cu * 16;
+    Buf s_id, s_key, d_counts, d_row0, d_row1, d_cell0, d_cell1, d_flags, d_tmp;
     const int64_t* d_id = nullptr;
     const int32_t* d_key = nullptr;
-    RN_HIP(dev::on_device(index_id, n, s_id, st, &d_id));
-    RN_HIP(dev::on_device(key, n, s_key, st, &d_key));
-    RN_HIP(d_counts.alloc(2 * sizeof(unsigned long long)));
-    RN_HIP(hipMemsetAsync(d_counts.p, 0, 2 * sizeof(unsigned long long), st));
-    RN_HIP(d_row0.alloc((size_t)n * 4));
-    RN_HIP(d_row1.alloc((size_t)n * 4));
-    RN_HIP(d_cell0.alloc((size_t)n * 8));
-    RN_HIP(d_cell1.alloc((size_t)n * 8));
-    RN_HIP(d_flags.alloc((size_t)n * 8));
-    hipLaunchKernelGGL(k_ci_check, dim3(blocks_for(n, wide)), dim3(kBlock), 0, st, d_key, n, d_row0.as<uint32_t>(),
+    MOSAIC_RC(dev::on_device(index_id, n, s_id, st, &d_id));
+    MOSAIC_RC(dev::on_device(key, n, s_key, st, &d_key));
+    MOSAIC_RC(d_counts.reserve(2 * sizeof(unsigned long long)));
+    MOSAIC_HIP(hipMemsetAsync(d_counts.p, 0, 2 * sizeof(unsigned long long), st));
+    MOSAIC_RC(d_row0.reserve((size_t)n * 4));
+    MOSAIC_RC(d_row1.reserve((size_t)n * 4));
+    MOSAIC_RC(d_cell0.reserve((size_t)n * 8));
+    MOSAIC_RC(d_cell1.reserve((size_t)n * 8));
+    MOSAIC_RC(d_flags.reserve((size_t)n * 8));
+    hipLaunchKernelGGL(k_ci_check, dim3(blocks_for(n, kBlock, wide)), dim3(kBlock), 0, st, d_key, n, d_row0.as<uint32_t>(),
                        d_counts.as<unsigned long long>());
-    RN_HIP(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long counts[2] = {0, 0};
-    RN_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-    RN_HIP(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     if (counts[0]) return mosaic_tess_fail(MOSAIC_E_ARG, ("cell index: " + std::to_string(counts[0]) + " chip(s) with a negative key").c_str());
     ix->max_row = (int64_t)counts[1] - 1;
     // by row, then (stable) by cell: (cell, row)
-    RN_RC(sort_pairs(d_row0.as<uint32_t>(), d_row1.as<uint32_t>(), d_id, d_cell0.as<int64_t>(), n, 0, bits_for((int64_t)counts[1]), st));
-    RN_RC(sort_pairs(d_cell0.as<int64_t>(), d_cell1.as<int64_t>(), d_row1.as<uint32_t>(), d_row0.as<uint32_t>(), n, 0, 64, st));
+    MOSAIC_RC(dev::sort_pairs(d_tmp, d_row0.as<uint32_t>(), d_row1.as<uint32_t>(), d_id, d_cell0.as<int64_t>(), (int)n, 0, bits_for((int64_t)counts[1]), st));
+    MOSAIC_RC(dev::sort_pairs(d_tmp, d_cell0.as<int64_t>(), d_cell1.as<int64_t>(), d_row1.as<uint32_t>(), d_row0.as<uint32_t>(), (int)n, 0, 64, st));
     const int64_t* cell = d_cell1.as<int64_t>();
     const uint32_t* row = d_row0.as<uint32_t>();
-    hipLaunchKernelGGL(k_ci_flags, dim3(blocks_for(n, wide)), dim3(kBlock), 0, st, cell, row, n, d_flags.as<uint64_t>());
-    RN_HIP(hipGetLastError());
-    size_t bytes = 0;
-    RN_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, d_flags.as<uint64_t>(), d_flags.as<uint64_t>(), (int)n, st));
-    RN_HIP(d_tmp.alloc(bytes));
-    RN_HIP(hipcub::DeviceScan::InclusiveSum(d_tmp.p, bytes, d_flags.as<uint64_t>(), d_flags.as<uint64_t>(), (int)n, st));
+    hipLaunchKernelGGL(k_ci_flags, dim3(blocks_for(n, kBlock, wide)), dim3(kBlock), 0, st, cell, row, n, d_flags.as<uint64_t>());
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_RC(dev::inclusive_sum(d_tmp, d_flags.as<uint64_t>(), d_flags.as<uint64_t>(), (int)n, st));
     uint64_t last = 0;
-    RN_HIP(hipMemcpyAsync(&last, d_flags.as<uint64_t>() + (n - 1), 8, hipMemcpyDeviceToHost, st));
-    RN_HIP(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipMemcpyAsync(&last, d_flags.as<uint64_t>() + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     ix->n_entries = (int64_t)(last & kLow32);
     ix->n_cells = (int64_t)(last >> 32);
-    RN_HIP(hipMalloc((void**)&ix->cells, (size_t)ix->n_cells * 8));
-    RN_HIP(hipMalloc((void**)&ix->start, (size_t)(ix->n_cells + 1) * 8));
-    RN_HIP(hipMalloc((void**)&ix->rows, (size_t)ix->n_entries * 4));
-    hipLaunchKernelGGL(k_ci_fill, dim3(blocks_for(n, wide)), dim3(kBlock), 0, st, cell, row, d_flags.as<uint64_t>(), n, ix->cells,
+    MOSAIC_HIP(hipMalloc((void**)&ix->cells, (size_t)ix->n_cells * 8));
+    MOSAIC_HIP(hipMalloc((void**)&ix->start, (size_t)(ix->n_cells + 1) * 8));
+    MOSAIC_HIP(hipMalloc((void**)&ix->rows, (size_t)ix->n_entries * 4));
+    hipLaunchKernelGGL(k_ci_fill, dim3(blocks_for(n, kBlock, wide)), dim3(kBlock), 0, st, cell, row, d_flags.as<uint64_t>(), n, ix->cells,
                        ix->start, ix->rows);
-    RN_HIP(hipGetLastError());
-    RN_HIP(hipMemcpyAsync(ix->start + ix->n_cells, &ix->n_entries, 8, hipMemcpyHostToDevice, st));
-    RN_HIP(hipMemsetAsync(d_counts.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_ci_max, dim3(blocks_for(ix->n_cells, wide)), dim3(kBlock), 0, st, ix->start, ix->n_cells,
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemcpyAsync(ix->start + ix->n_cells, &ix->n_entries, 8, hipMemcpyHostToDevice, st));
+    MOSAIC_HIP(hipMemsetAsync(d_counts.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_ci_max, dim3(blocks_for(ix->n_cells, kBlock, wide)), dim3(kBlock), 0, st, ix->start, ix->n_cells,
                        d_counts.as<unsigned long long>());
-    RN_HIP(hipGetLastError());
-    RN_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    RN_HIP(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     ix->max_per_cell = (int64_t)counts[0];
     *out = ix.release();
     return MOSAIC_OK;
@@ -354,55 +308,51 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
         return mosaic_tess_fail(MOSAIC_E_ARG, "ring_neighbours: 2^31 - 1 rows at the most");
     if (index->max_row >= right->n_geoms)
         return mosaic_tess_fail(MOSAIC_E_ARG, "ring_neighbours: the cell index names a row outside the candidate column");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    RN_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    if (left->device != device || right->device != device || index->device != device)
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    if (left->device != ex.device || right->device != ex.device || index->device != ex.device)
         return mosaic_tess_fail(MOSAIC_E_ARG, "ring_neighbours: a geometry column or cell index of another device");
-    hipStream_t st = (hipStream_t)stream_v;
-    const int64_t wide = (int64_t)n_cu * 16;
+    hipStream_t st = ex.stream;
+    const int64_t wide = (int64_t)ex.n_cu * 16;
     const int64_t n_left = left->n_geoms;
     g_last_ms[0] = g_last_ms[1] = g_last_ms[2] = 0;
 
     std::unique_ptr<mosaic_neighbours> nb(new mosaic_neighbours());
-    nb->device = device;
+    nb->device = ex.device;
     nb->n_left = n_left;
-    Events ev;
-    for (hipEvent_t& e : ev.e) RN_HIP(hipEventCreate(&e));
-    RN_HIP(hipEventRecord(ev.e[0], st));
+    dev::Events<4> ev;
+    MOSAIC_RC(ev.create());
+    MOSAIC_HIP(hipEventRecord(ev.e[0], st));
 
-    DevMem s_lrow, s_cell, d_un, d_slot, d_cnt, d_off, d_bad, d_tmp, d_k0, d_k1, d_num, d_keep;
-    RN_HIP(d_un.alloc((size_t)n_left * 4));
-    RN_HIP(hipMemsetAsync(d_un.p, 0, std::max<size_t>((size_t)n_left * 4, 16), st));
-    RN_HIP(hipMalloc((void**)&nb->unmatched, std::max<size_t>((size_t)n_left, 16)));
-    RN_HIP(d_num.alloc(8));
+    Buf s_lrow, s_cell, d_un, d_slot, d_cnt, d_off, d_bad, d_tmp, d_k0, d_k1, d_num, d_keep;
+    MOSAIC_RC(d_un.reserve((size_t)n_left * 4));
+    MOSAIC_HIP(hipMemsetAsync(d_un.p, 0, std::max<size_t>((size_t)n_left * 4, 16), st));
+    MOSAIC_HIP(hipMalloc((void**)&nb->unmatched, std::max<size_t>((size_t)n_left, 16)));
+    MOSAIC_RC(d_num.reserve(8));
     int64_t total = 0;
     const int64_t* d_lrow = nullptr;
     const int64_t* d_cell = nullptr;
     const rn::CellIndexView ix{index->cells, index->start, index->rows, index->n_cells};
     if (n > 0) {
-        RN_HIP(dev::on_device(left_row, n, s_lrow, st, &d_lrow));
-        RN_HIP(dev::on_device(cell, n, s_cell, st, &d_cell));
-        RN_HIP(d_slot.alloc((size_t)n * 4));
-        RN_HIP(d_cnt.alloc((size_t)n * 8));
-        RN_HIP(d_off.alloc((size_t)(n + 1) * 8));
-        RN_HIP(d_bad.alloc(8));
-        RN_HIP(hipMemsetAsync(d_bad.p, 0, 8, st));
-        RN_HIP(hipMemsetAsync(d_off.p, 0, 8, st));
+        MOSAIC_RC(dev::on_device(left_row, n, s_lrow, st, &d_lrow));
+        MOSAIC_RC(dev::on_device(cell, n, s_cell, st, &d_cell));
+        MOSAIC_RC(d_slot.reserve((size_t)n * 4));
+        MOSAIC_RC(d_cnt.reserve((size_t)n * 8));
+        MOSAIC_RC(d_off.reserve((size_t)(n + 1) * 8));
+        MOSAIC_RC(d_bad.reserve(8));
+        MOSAIC_HIP(hipMemsetAsync(d_bad.p, 0, 8, st));
+        MOSAIC_HIP(hipMemsetAsync(d_off.p, 0, 8, st));
         CountArgs ca{ix, d_lrow, d_cell, n, n_left, d_slot.as<int32_t>(), d_cnt.as<uint64_t>(), d_un.as<uint32_t>(),
                      d_bad.as<unsigned long long>()};
-        hipLaunchKernelGGL(k_rn_count, dim3(blocks_for(n, wide)), dim3(kBlock), 0, st, ca);
-        RN_HIP(hipGetLastError());
-        size_t bytes = 0;
+        hipLaunchKernelGGL(k_rn_count, dim3(blocks_for(n, kBlock, wide)), dim3(kBlock), 0, st, ca);
+        MOSAIC_HIP(hipGetLastError());
         // off[0] = 0, off[i + 1] = cnt[0] + .. + cnt[i]: off[n] is the number of hits
-        RN_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, d_cnt.as<uint64_t>(), d_off.as<uint64_t>() + 1, (int)n, st));
-        RN_HIP(d_tmp.alloc(bytes));
-        RN_HIP(hipcub::DeviceScan::InclusiveSum(d_tmp.p, bytes, d_cnt.as<uint64_t>(), d_off.as<uint64_t>() + 1, (int)n, st));
+        MOSAIC_RC(dev::inclusive_sum(d_tmp, d_cnt.as<uint64_t>(), d_off.as<uint64_t>() + 1, (int)n, st));
         unsigned long long bad = 0;
         uint64_t tot = 0;
-        RN_HIP(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
-        RN_HIP(hipMemcpyAsync(&tot, d_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-        RN_HIP(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipMemcpyAsync(&tot, d_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
         if (bad)
             return mosaic_tess_fail(MOSAIC_E_ARG, ("ring_neighbours: " + std::to_string(bad) + " row(s) name a landmark outside its column").c_str());
         if (tot >= (uint64_t)rn::kMaxRows)
@@ -410,74 +360,74 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
                                                         " (landmark, candidate) hits in one call, 2^31 - 1 at the most: pass fewer rows").c_str());
         total = (int64_t)tot;
     }
-    hipLaunchKernelGGL(k_rn_narrow, dim3(blocks_for(n_left, wide)), dim3(kBlock), 0, st, d_un.as<uint32_t>(), n_left, nb->unmatched);
-    RN_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_rn_narrow, dim3(blocks_for(n_left, kBlock, wide)), dim3(kBlock), 0, st, d_un.as<uint32_t>(), n_left, nb->unmatched);
+    MOSAIC_HIP(hipGetLastError());
 
     int64_t n_pairs = 0;
     uint64_t* pairs = nullptr;  // (landmark, candidate) keys, distinct and ascending
     if (total > 0) {
-        RN_HIP(d_k0.alloc((size_t)total * 8));
-        RN_HIP(d_k1.alloc((size_t)total * 8));
-        hipLaunchKernelGGL(k_rn_emit, dim3(blocks_for(total, wide)), dim3(kBlock), 0, st, ix, d_lrow, d_slot.as<int32_t>(),
+        MOSAIC_RC(d_k0.reserve((size_t)total * 8));
+        MOSAIC_RC(d_k1.reserve((size_t)total * 8));
+        hipLaunchKernelGGL(k_rn_emit, dim3(blocks_for(total, kBlock, wide)), dim3(kBlock), 0, st, ix, d_lrow, d_slot.as<int32_t>(),
                            d_off.as<uint64_t>(), n, total, d_k0.as<uint64_t>());
-        RN_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
         size_t bytes = 0;
         const int end_bit = 32 + bits_for(n_left);
-        RN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
-        DevMem t1, t2, t3;
-        RN_HIP(t1.alloc(bytes));
-        RN_HIP(hipcub::DeviceRadixSort::SortKeys(t1.p, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
+        MOSAIC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
+        Buf t1, t2, t3;
+        MOSAIC_RC(t1.reserve(bytes));
+        MOSAIC_HIP(hipcub::DeviceRadixSort::SortKeys(t1.p, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
         bytes = 0;
-        RN_HIP(hipcub::DeviceSelect::Unique(nullptr, bytes, d_k1.as<uint64_t>(), d_k0.as<uint64_t>(), d_num.as<int64_t>(), (int)total, st));
-        RN_HIP(t2.alloc(bytes));
-        RN_HIP(hipcub::DeviceSelect::Unique(t2.p, bytes, d_k1.as<uint64_t>(), d_k0.as<uint64_t>(), d_num.as<int64_t>(), (int)total, st));
-        RN_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
-        RN_HIP(hipStreamSynchronize(st));
+        MOSAIC_HIP(hipcub::DeviceSelect::Unique(nullptr, bytes, d_k1.as<uint64_t>(), d_k0.as<uint64_t>(), d_num.as<int64_t>(), (int)total, st));
+        MOSAIC_RC(t2.reserve(bytes));
+        MOSAIC_HIP(hipcub::DeviceSelect::Unique(t2.p, bytes, d_k1.as<uint64_t>(), d_k0.as<uint64_t>(), d_num.as<int64_t>(), (int)total, st));
+        MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
         pairs = d_k0.as<uint64_t>();
         if (!keep_self && n_pairs > 0) {
-            RN_HIP(d_keep.alloc((size_t)n_pairs));
-            hipLaunchKernelGGL(k_rn_self, dim3(blocks_for(n_pairs, wide)), dim3(kBlock), 0, st, view(left), view(right), pairs, n_pairs,
+            MOSAIC_RC(d_keep.reserve((size_t)n_pairs));
+            hipLaunchKernelGGL(k_rn_self, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, view(left), view(right), pairs, n_pairs,
                                d_keep.as<uint8_t>());
-            RN_HIP(hipGetLastError());
+            MOSAIC_HIP(hipGetLastError());
             bytes = 0;
-            RN_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
+            MOSAIC_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
                                                  (int)n_pairs, st));
-            RN_HIP(t3.alloc(bytes));
-            RN_HIP(hipcub::DeviceSelect::Flagged(t3.p, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
+            MOSAIC_RC(t3.reserve(bytes));
+            MOSAIC_HIP(hipcub::DeviceSelect::Flagged(t3.p, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
                                                  (int)n_pairs, st));
-            RN_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
-            RN_HIP(hipStreamSynchronize(st));
+            MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
+            MOSAIC_HIP(hipStreamSynchronize(st));
             pairs = d_k1.as<uint64_t>();
         }
     }
     nb->n_pairs = n_pairs;
     const size_t pb = std::max<size_t>((size_t)n_pairs * 8, 16);
-    RN_HIP(hipMalloc((void**)&nb->left_row, pb));
-    RN_HIP(hipMalloc((void**)&nb->right_row, pb));
-    RN_HIP(hipMalloc((void**)&nb->distance, pb));
+    MOSAIC_HIP(hipMalloc((void**)&nb->left_row, pb));
+    MOSAIC_HIP(hipMalloc((void**)&nb->right_row, pb));
+    MOSAIC_HIP(hipMalloc((void**)&nb->distance, pb));
     if (n_pairs > 0) {
-        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, wide)), dim3(kBlock), 0, st, pairs, n_pairs, nb->left_row,
+        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, pairs, n_pairs, nb->left_row,
                            nb->right_row);
-        RN_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    RN_HIP(hipEventRecord(ev.e[1], st));
-    if (n_pairs > 0) RN_RC(mosaic_st_distance(ctx, left, right, nb->left_row, nb->right_row, n_pairs, nb->distance, nullptr));
-    RN_HIP(hipEventRecord(ev.e[2], st));
+    MOSAIC_HIP(hipEventRecord(ev.e[1], st));
+    if (n_pairs > 0) MOSAIC_RC(mosaic_st_distance(ctx, left, right, nb->left_row, nb->right_row, n_pairs, nb->distance, nullptr));
+    MOSAIC_HIP(hipEventRecord(ev.e[2], st));
     if (n_pairs > 0) {
         // `pairs` is ordered by (landmark, candidate): stable by distance bits, then stable by landmark (the
         // second sort leaves the distances in the result's own array)
-        DevMem d_d1, d_p1;
-        RN_HIP(d_d1.alloc((size_t)n_pairs * 8));
-        RN_HIP(d_p1.alloc((size_t)n_pairs * 8));
+        Buf d_d1, d_p1;
+        MOSAIC_RC(d_d1.reserve((size_t)n_pairs * 8));
+        MOSAIC_RC(d_p1.reserve((size_t)n_pairs * 8));
         uint64_t* other = pairs == d_k0.as<uint64_t>() ? d_k1.as<uint64_t>() : d_k0.as<uint64_t>();
-        RN_RC(sort_pairs((const uint64_t*)nb->distance, d_d1.as<uint64_t>(), pairs, d_p1.as<uint64_t>(), n_pairs, 0, 64, st));
-        RN_RC(sort_pairs(d_p1.as<uint64_t>(), other, d_d1.as<uint64_t>(), (uint64_t*)nb->distance, n_pairs, 32, 32 + bits_for(n_left), st));
-        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, wide)), dim3(kBlock), 0, st, other, n_pairs, nb->left_row,
+        MOSAIC_RC(dev::sort_pairs(d_tmp, (const uint64_t*)nb->distance, d_d1.as<uint64_t>(), pairs, d_p1.as<uint64_t>(), (int)n_pairs, 0, 64, st));
+        MOSAIC_RC(dev::sort_pairs(d_tmp, d_p1.as<uint64_t>(), other, d_d1.as<uint64_t>(), (uint64_t*)nb->distance, (int)n_pairs, 32, 32 + bits_for(n_left), st));
+        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, other, n_pairs, nb->left_row,
                            nb->right_row);
-        RN_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    RN_HIP(hipEventRecord(ev.e[3], st));
-    RN_HIP(hipStreamSynchronize(st));
+    MOSAIC_HIP(hipEventRecord(ev.e[3], st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < 3; i++) {
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]);
@@ -496,12 +446,12 @@ int mosaic_neighbours_info(const mosaic_neighbours* nb, int64_t* n_pairs, int64_
 
 int mosaic_neighbours_export(const mosaic_neighbours* nb, int64_t* left_row, int64_t* right_row, double* distance, uint8_t* unmatched) {
     if (!nb) return mosaic_tess_fail(MOSAIC_E_ARG, "null neighbours");
-    RN_HIP(hipSetDevice(nb->device));
+    MOSAIC_HIP(hipSetDevice(nb->device));
     const size_t pb = (size_t)nb->n_pairs * 8;
-    if (left_row && pb) RN_HIP(hipMemcpy(left_row, nb->left_row, pb, hipMemcpyDefault));
-    if (right_row && pb) RN_HIP(hipMemcpy(right_row, nb->right_row, pb, hipMemcpyDefault));
-    if (distance && pb) RN_HIP(hipMemcpy(distance, nb->distance, pb, hipMemcpyDefault));
-    if (unmatched && nb->n_left) RN_HIP(hipMemcpy(unmatched, nb->unmatched, (size_t)nb->n_left, hipMemcpyDefault));
+    if (left_row && pb) MOSAIC_HIP(hipMemcpy(left_row, nb->left_row, pb, hipMemcpyDefault));
+    if (right_row && pb) MOSAIC_HIP(hipMemcpy(right_row, nb->right_row, pb, hipMemcpyDefault));
+    if (distance && pb) MOSAIC_HIP(hipMemcpy(distance, nb->distance, pb, hipMemcpyDefault));
+    if (unmatched && nb->n_left) MOSAIC_HIP(hipMemcpy(unmatched, nb->unmatched, (size_t)nb->n_left, hipMemcpyDefault));
     return MOSAIC_OK;
 }
 

@@ -28,15 +28,9 @@
 //                  skipped only when dist::box_lower_bound of it is strictly greater than that minimum,
 //                  and a minimum of 0 ends the pair.  The lanes' minima are reduced within each wave by
 //                  shuffles, then across the waves through LDS.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
 #include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/mosaic_hip.h"
+#include "dev_rt.h"
 #include "geoms_build.h"
 #include "geoms_device.h"
 #include "pair_lists.h"
@@ -44,33 +38,16 @@
 
 using namespace mosaic;
 
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune);
-
 namespace {
 
-using pairs::blocks_for;
+using dev::blocks_for;
+using dev::Buf;
+using dev::is_device_ptr;
 using pairs::Col;
 using pairs::kBlock;
 using pairs::view;
 using pairs::wave_append;
 constexpr int kMaxTile = 1024;
-
-#define SD_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define SD_HIP(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess)                                                                                 \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                \
-                                    (std::string("st_distance: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
-using dev::is_device_ptr;
 
 // a point column built on the device: row i is the point part (x[i], y[i]); a NaN coordinate is POINT EMPTY
 __global__ void __launch_bounds__(kBlock) k_points_col(const double* x, const double* y, int64_t n, pip::Vec2* verts,
@@ -302,8 +279,8 @@ __global__ void __launch_bounds__(kBlock) k_dist_block(DistArgs a) {
 
 template <class T>
 int upload(T** dst, const std::vector<T>& src) {
-    SD_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
-    if (!src.empty()) SD_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    MOSAIC_HIP(hipMalloc((void**)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
+    if (!src.empty()) MOSAIC_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return MOSAIC_OK;
 }
 
@@ -314,15 +291,15 @@ int upload_column(int device, const GeomColumn& c, mosaic_geoms** out) {
     g->n_geoms = c.size();
     g->n_vertices = (int64_t)c.b.verts.size();
     g->n_row_path = c.n_row_path;
-    SD_RC(upload(&g->verts, c.b.verts));
-    SD_RC(upload(&g->ring_start, c.b.ring_start));
-    SD_RC(upload(&g->ring_bbox, c.b.ring_bbox));
-    SD_RC(upload(&g->part_ring, c.b.part_ring));
-    SD_RC(upload(&g->part_kind, c.part_kind));
-    SD_RC(upload(&g->geom_part, c.b.geom_part));
-    SD_RC(upload(&g->geom_bbox, c.b.geom_bbox));
-    SD_RC(upload(&g->geom_facets, c.geom_facets));
-    SD_RC(upload(&g->row_status, c.row_status));
+    MOSAIC_RC(upload(&g->verts, c.b.verts));
+    MOSAIC_RC(upload(&g->ring_start, c.b.ring_start));
+    MOSAIC_RC(upload(&g->ring_bbox, c.b.ring_bbox));
+    MOSAIC_RC(upload(&g->part_ring, c.b.part_ring));
+    MOSAIC_RC(upload(&g->part_kind, c.part_kind));
+    MOSAIC_RC(upload(&g->geom_part, c.b.geom_part));
+    MOSAIC_RC(upload(&g->geom_bbox, c.b.geom_bbox));
+    MOSAIC_RC(upload(&g->geom_facets, c.geom_facets));
+    MOSAIC_RC(upload(&g->row_status, c.row_status));
     *out = g.release();
     return MOSAIC_OK;
 }
@@ -338,9 +315,8 @@ int mosaic_geoms_create_wkb_ex(mosaic_ctx* ctx, int64_t n, const int64_t* offset
     if (!ctx || !out || n < 0 || (n > 0 && (!offsets || !wkb))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
     if (flags & ~(uint32_t)MOSAIC_GEOMS_LINES) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: unknown flag");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
     GeomColumn c;
     c.lines = (flags & MOSAIC_GEOMS_LINES) != 0;
     for (int64_t i = 0; i < n; i++) {
@@ -350,7 +326,7 @@ int mosaic_geoms_create_wkb_ex(mosaic_ctx* ctx, int64_t n, const int64_t* offset
         else
             c.add_wkb(wkb + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     }
-    return upload_column(device, c, out);
+    return upload_column(ex.device, c, out);
 }
 
 int mosaic_geoms_create_wkb(mosaic_ctx* ctx, int64_t n, const int64_t* offsets, const uint8_t* wkb, const uint8_t* valid,
@@ -366,13 +342,12 @@ int mosaic_geoms_create_lines(mosaic_ctx* ctx, int64_t n, const int64_t* geom_li
     for (int64_t g = 0; g < n; g++)
         if (geom_lines[g + 1] < geom_lines[g]) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
     if (geom_lines[n] > 0 && !xy) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
     GeomColumn c;
     c.lines = true;
     if (!c.add_lines(n, geom_lines, line_offsets, xy)) return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
-    return upload_column(device, c, out);
+    return upload_column(ex.device, c, out);
 }
 
 int mosaic_geoms_create_arrays(mosaic_ctx* ctx, int64_t n, const int64_t* geom_parts, const int64_t* part_rings,
@@ -380,52 +355,50 @@ int mosaic_geoms_create_arrays(mosaic_ctx* ctx, int64_t n, const int64_t* geom_p
     if (!ctx || !out || n < 0 || !geom_parts || (n > 0 && (!part_rings || !ring_offsets)))
         return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream = nullptr;
-    SD_RC(mosaic_ctx_exec(ctx, &device, &stream, &jdk, &n_cu));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
     GeomColumn c;
     if (geom_parts[0] != 0 || !c.add_arrays(n, geom_parts, part_rings, ring_offsets, xy))
         return mosaic_tess_fail(MOSAIC_E_ARG, "geometry column: inconsistent offsets");
-    return upload_column(device, c, out);
+    return upload_column(ex.device, c, out);
 }
 
 int mosaic_geoms_create_points(mosaic_ctx* ctx, const double* x, const double* y, int64_t n, mosaic_geoms** out) {
     if (!ctx || !out || n < 0 || (n > 0 && (!x || !y))) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
     *out = nullptr;
     if (n >= 0xffffffffLL) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "geometry column: 2^32 - 1 vertices or rows at the most");
-    int device = 0, jdk = 8, n_cu = 256;
-    void* stream_v = nullptr;
-    SD_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    hipStream_t stream = (hipStream_t)stream_v;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    hipStream_t stream = ex.stream;
     std::unique_ptr<mosaic_geoms> g(new mosaic_geoms());
-    g->device = device;
+    g->device = ex.device;
     g->n_geoms = n;
     g->n_vertices = n;
     const size_t n1 = (size_t)n + 1;
-    SD_HIP(hipMalloc((void**)&g->verts, n1 * sizeof(pip::Vec2)));
-    SD_HIP(hipMalloc((void**)&g->ring_start, n1 * sizeof(uint32_t)));
-    SD_HIP(hipMalloc((void**)&g->ring_bbox, n1 * sizeof(pip::Box)));
-    SD_HIP(hipMalloc((void**)&g->part_ring, n1 * sizeof(uint32_t)));
-    SD_HIP(hipMalloc((void**)&g->part_kind, n1));
-    SD_HIP(hipMalloc((void**)&g->geom_part, n1 * sizeof(uint32_t)));
-    SD_HIP(hipMalloc((void**)&g->geom_bbox, n1 * sizeof(pip::Box)));
-    SD_HIP(hipMalloc((void**)&g->geom_facets, n1 * sizeof(uint32_t)));
-    SD_HIP(hipMalloc((void**)&g->row_status, n1 * sizeof(int32_t)));
-    DevMem sx, sy, cnt;
+    MOSAIC_HIP(hipMalloc((void**)&g->verts, n1 * sizeof(pip::Vec2)));
+    MOSAIC_HIP(hipMalloc((void**)&g->ring_start, n1 * sizeof(uint32_t)));
+    MOSAIC_HIP(hipMalloc((void**)&g->ring_bbox, n1 * sizeof(pip::Box)));
+    MOSAIC_HIP(hipMalloc((void**)&g->part_ring, n1 * sizeof(uint32_t)));
+    MOSAIC_HIP(hipMalloc((void**)&g->part_kind, n1));
+    MOSAIC_HIP(hipMalloc((void**)&g->geom_part, n1 * sizeof(uint32_t)));
+    MOSAIC_HIP(hipMalloc((void**)&g->geom_bbox, n1 * sizeof(pip::Box)));
+    MOSAIC_HIP(hipMalloc((void**)&g->geom_facets, n1 * sizeof(uint32_t)));
+    MOSAIC_HIP(hipMalloc((void**)&g->row_status, n1 * sizeof(int32_t)));
+    Buf sx, sy, cnt;
     const double *dx = nullptr, *dy = nullptr;
     if (n > 0) {
-        SD_HIP(dev::on_device(x, n, sx, stream, &dx));
-        SD_HIP(dev::on_device(y, n, sy, stream, &dy));
+        MOSAIC_RC(dev::on_device(x, n, sx, stream, &dx));
+        MOSAIC_RC(dev::on_device(y, n, sy, stream, &dy));
     }
-    SD_HIP(cnt.alloc(sizeof(unsigned long long)));
-    SD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(k_points_col, dim3((unsigned)blocks_for(n + 1, (int64_t)n_cu * 16)), dim3(kBlock), 0, stream, dx, dy, n,
+    MOSAIC_RC(cnt.reserve(sizeof(unsigned long long)));
+    MOSAIC_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_points_col, dim3((unsigned)blocks_for(n + 1, kBlock, (int64_t)ex.n_cu * 16)), dim3(kBlock), 0, stream, dx, dy, n,
                        g->verts, g->ring_start, g->ring_bbox, g->part_ring, g->part_kind, g->geom_part, g->geom_bbox,
                        g->geom_facets, g->row_status, (unsigned long long*)cnt.p);
-    SD_HIP(hipGetLastError());
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long n_path = 0;
-    SD_HIP(hipMemcpyAsync(&n_path, cnt.p, sizeof(n_path), hipMemcpyDeviceToHost, stream));
-    SD_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipMemcpyAsync(&n_path, cnt.p, sizeof(n_path), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     g->n_row_path = (int64_t)n_path;
     *out = g.release();
     return MOSAIC_OK;
@@ -454,37 +427,37 @@ int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_g
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: left_row and right_row are both given or both null");
     if (!left_row && (n_pairs > left->n_geoms || n_pairs > right->n_geoms))
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: row-wise form with more pairs than rows");
-    int device = 0, jdk = 8, n_cu = 256, tile = 16, prune = 1;
+    int tile = 16, prune = 1;
     int64_t small_work = 512;
-    void* stream_v = nullptr;
-    SD_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    SD_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
-    if (left->device != device || right->device != device)
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    MOSAIC_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
+    if (left->device != ex.device || right->device != ex.device)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: a geometry column of another device");
     if (n_pairs == 0) return MOSAIC_OK;
     tile = std::max(1, std::min(tile, kMaxTile));
-    hipStream_t stream = (hipStream_t)stream_v;
+    hipStream_t stream = ex.stream;
     const int64_t n = n_pairs;
 
-    DevMem s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
+    Buf s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
     PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
     if (left_row) {
-        SD_HIP(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
-        SD_HIP(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
+        MOSAIC_RC(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
+        MOSAIC_RC(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
     }
-    SD_HIP(s_plan.alloc((size_t)n * sizeof(int32_t)));
-    SD_HIP(s_list.alloc((size_t)n * sizeof(int64_t)));
-    SD_HIP(s_counts.alloc(4 * sizeof(unsigned long long)));
-    SD_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
+    MOSAIC_RC(s_plan.reserve((size_t)n * sizeof(int32_t)));
+    MOSAIC_RC(s_list.reserve((size_t)n * sizeof(int64_t)));
+    MOSAIC_RC(s_counts.reserve(4 * sizeof(unsigned long long)));
+    MOSAIC_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
     pa.plan = (int32_t*)s_plan.p;
     pa.list = (int64_t*)s_list.p;
     pa.counts = (unsigned long long*)s_counts.p;
-    const int64_t wide = (int64_t)n_cu * 16;
-    hipLaunchKernelGGL(k_dist_plan, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa);
-    SD_HIP(hipGetLastError());
+    const int64_t wide = (int64_t)ex.n_cu * 16;
+    hipLaunchKernelGGL(k_dist_plan, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa);
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long counts[4] = {0, 0, 0, 0};
-    SD_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    SD_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     if (counts[2])
         return mosaic_tess_fail(MOSAIC_E_ARG, ("st_distance: " + std::to_string(counts[2]) + " pair(s) name a row outside their column").c_str());
 
@@ -492,29 +465,29 @@ int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_g
     double* d_out = out;
     int32_t* d_status = status;
     if (!dev_out) {
-        SD_HIP(s_out.alloc((size_t)n * sizeof(double)));
+        MOSAIC_RC(s_out.reserve((size_t)n * sizeof(double)));
         d_out = (double*)s_out.p;
     }
     if (!dev_status) {
-        SD_HIP(s_status.alloc((size_t)n * sizeof(int32_t)));
+        MOSAIC_RC(s_status.reserve((size_t)n * sizeof(int32_t)));
         d_status = (int32_t*)s_status.p;
     }
-    hipLaunchKernelGGL(k_dist_fill, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
-    SD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_dist_fill, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
+    MOSAIC_HIP(hipGetLastError());
     DistArgs da{pa.L, pa.R, pa.lrow, pa.rrow, pa.list, (int64_t)counts[0], d_out, tile, prune};
     if (counts[0]) {
-        hipLaunchKernelGGL(k_dist_small, dim3((unsigned)blocks_for((int64_t)counts[0], wide)), dim3(kBlock), 0, stream, da);
-        SD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_dist_small, dim3((unsigned)blocks_for((int64_t)counts[0], kBlock, wide)), dim3(kBlock), 0, stream, da);
+        MOSAIC_HIP(hipGetLastError());
     }
     if (counts[1]) {
         da.list = pa.list + (n - (int64_t)counts[1]);
         da.n_list = (int64_t)counts[1];
         hipLaunchKernelGGL(k_dist_block, dim3((unsigned)std::min<int64_t>(da.n_list, (int64_t)1 << 20)), dim3(kBlock), 0, stream, da);
-        SD_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    if (!dev_out) SD_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (!dev_status) SD_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    SD_HIP(hipStreamSynchronize(stream));
+    if (!dev_out) MOSAIC_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (!dev_status) MOSAIC_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     return MOSAIC_OK;
 }
 

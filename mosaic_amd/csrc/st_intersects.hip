@@ -23,13 +23,7 @@
 //                  component, direction) task, the component's first vertex located by the
 //                  wave-cooperative locate of pip_coop.h (its flags per segment are those of
 //                  pip::locate_in_ring, see that header), until a task hits.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
-#include <string>
-
-#include "../../include/mosaic_hip.h"
+#include "dev_rt.h"
 #include "geoms_device.h"
 #include "pair_lists.h"
 #include "pip_coop.h"
@@ -37,34 +31,17 @@
 
 using namespace mosaic;
 
-extern "C" int mosaic_tess_fail(int code, const char* msg);
-extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune);
-
 namespace {
 
-using pairs::blocks_for;
+using dev::blocks_for;
+using dev::Buf;
+using dev::is_device_ptr;
 using pairs::Col;
 using pairs::kBlock;
 using pairs::view;
 using pairs::wave_append;
 constexpr int kMaxTile = 1024;
 constexpr int kWaves = kBlock / 64;
-
-#define SI_RC(expr)          \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
-#define SI_HIP(expr)                                                                                            \
-    do {                                                                                                        \
-        hipError_t _e = (expr);                                                                                 \
-        if (_e != hipSuccess)                                                                                   \
-            return mosaic_tess_fail(_e == hipErrorOutOfMemory ? MOSAIC_E_NOMEM : MOSAIC_E_HIP,                  \
-                                    (std::string("st_intersects: ") + hipGetErrorString(_e) + " at " #expr).c_str()); \
-    } while (0)
-
-using dev::DevMem;
-using dev::is_device_ptr;
 
 // the last call of this thread: pairs ended in the plan kernel, on the one-lane list, on the workgroup list
 thread_local int64_t t_last[3] = {0, 0, 0};
@@ -267,38 +244,38 @@ int mosaic_st_intersects(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersects: left_row and right_row are both given or both null");
     if (!left_row && (n_pairs > left->n_geoms || n_pairs > right->n_geoms))
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersects: row-wise form with more pairs than rows");
-    int device = 0, jdk = 8, n_cu = 256, tile = 16, prune = 1;
+    int tile = 16, prune = 1;
     int64_t small_work = 512;
-    void* stream_v = nullptr;
-    SI_RC(mosaic_ctx_exec(ctx, &device, &stream_v, &jdk, &n_cu));
-    SI_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
-    if (left->device != device || right->device != device)
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    MOSAIC_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
+    if (left->device != ex.device || right->device != ex.device)
         return mosaic_tess_fail(MOSAIC_E_ARG, "st_intersects: a geometry column of another device");
     t_last[0] = t_last[1] = t_last[2] = 0;
     if (n_pairs == 0) return MOSAIC_OK;
     tile = std::max(1, std::min(tile, kMaxTile));
-    hipStream_t stream = (hipStream_t)stream_v;
+    hipStream_t stream = ex.stream;
     const int64_t n = n_pairs;
 
-    DevMem s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
+    Buf s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
     PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
     if (left_row) {
-        SI_HIP(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
-        SI_HIP(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
+        MOSAIC_RC(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
+        MOSAIC_RC(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
     }
-    SI_HIP(s_plan.alloc((size_t)n * sizeof(int32_t)));
-    SI_HIP(s_list.alloc((size_t)n * sizeof(int64_t)));
-    SI_HIP(s_counts.alloc(4 * sizeof(unsigned long long)));
-    SI_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
+    MOSAIC_RC(s_plan.reserve((size_t)n * sizeof(int32_t)));
+    MOSAIC_RC(s_list.reserve((size_t)n * sizeof(int64_t)));
+    MOSAIC_RC(s_counts.reserve(4 * sizeof(unsigned long long)));
+    MOSAIC_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
     pa.plan = (int32_t*)s_plan.p;
     pa.list = (int64_t*)s_list.p;
     pa.counts = (unsigned long long*)s_counts.p;
-    const int64_t wide = (int64_t)n_cu * 16;
-    hipLaunchKernelGGL(k_isect_plan, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa);
-    SI_HIP(hipGetLastError());
+    const int64_t wide = (int64_t)ex.n_cu * 16;
+    hipLaunchKernelGGL(k_isect_plan, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa);
+    MOSAIC_HIP(hipGetLastError());
     unsigned long long counts[4] = {0, 0, 0, 0};
-    SI_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    SI_HIP(hipStreamSynchronize(stream));
+    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     if (counts[2])
         return mosaic_tess_fail(MOSAIC_E_ARG, ("st_intersects: " + std::to_string(counts[2]) + " pair(s) name a row outside their column").c_str());
 
@@ -306,29 +283,29 @@ int mosaic_st_intersects(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic
     uint8_t* d_out = out;
     int32_t* d_status = status;
     if (!dev_out) {
-        SI_HIP(s_out.alloc((size_t)n));
+        MOSAIC_RC(s_out.reserve((size_t)n));
         d_out = (uint8_t*)s_out.p;
     }
     if (!dev_status) {
-        SI_HIP(s_status.alloc((size_t)n * sizeof(int32_t)));
+        MOSAIC_RC(s_status.reserve((size_t)n * sizeof(int32_t)));
         d_status = (int32_t*)s_status.p;
     }
-    hipLaunchKernelGGL(k_isect_fill, dim3((unsigned)blocks_for(n, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
-    SI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_isect_fill, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
+    MOSAIC_HIP(hipGetLastError());
     IsectArgs ia{pa.L, pa.R, pa.lrow, pa.rrow, pa.list, (int64_t)counts[0], d_out, tile};
     if (counts[0]) {
-        hipLaunchKernelGGL(k_isect_small, dim3((unsigned)blocks_for((int64_t)counts[0], wide)), dim3(kBlock), 0, stream, ia);
-        SI_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_isect_small, dim3((unsigned)blocks_for((int64_t)counts[0], kBlock, wide)), dim3(kBlock), 0, stream, ia);
+        MOSAIC_HIP(hipGetLastError());
     }
     if (counts[1]) {
         ia.list = pa.list + (n - (int64_t)counts[1]);
         ia.n_list = (int64_t)counts[1];
         hipLaunchKernelGGL(k_isect_block, dim3((unsigned)std::min<int64_t>(ia.n_list, (int64_t)1 << 20)), dim3(kBlock), 0, stream, ia);
-        SI_HIP(hipGetLastError());
+        MOSAIC_HIP(hipGetLastError());
     }
-    if (!dev_out) SI_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, stream));
-    if (!dev_status) SI_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    SI_HIP(hipStreamSynchronize(stream));
+    if (!dev_out) MOSAIC_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, stream));
+    if (!dev_status) MOSAIC_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    MOSAIC_HIP(hipStreamSynchronize(stream));
     t_last[0] = n - (int64_t)counts[0] - (int64_t)counts[1];
     t_last[1] = (int64_t)counts[0];
     t_last[2] = (int64_t)counts[1];

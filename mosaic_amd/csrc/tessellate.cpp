@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/mosaic_hip.h"
+#include "fail.h"
 #include "tess_gpu.h"
 #include "tess_records.h"
 #include "bng_device.h"
@@ -47,7 +48,6 @@
 using namespace mosaic;
 using tessclip::ClippedChips;  // the GPU-clipped border chips by candidate (tess_records.h)
 
-extern "C" int mosaic_tess_fail(int code, const char* msg);  // defined in mosaic_hip.hip
 extern "C" int mosaic_tess_classify_bng(mosaic_ctx* c, int64_t n_geoms, const int64_t* geom_parts,
                                         const int64_t* part_rings, const int64_t* ring_offsets, const double* xy,
                                         int64_t n_cand, const int32_t* cand_geom, const int64_t* cand_ij, double e,

@@ -132,3 +132,31 @@ def test_translation_units_agree_on_struct_layouts():
         f.argtypes = []
         fps.append(f())
     assert fps[0] == fps[1] and all(fps)
+
+
+# one entry point of each feature translation unit, called without a context: (name, trailing arguments)
+_NULL_CTX_CALLS = [
+    ("mosaic_polyfill", lambda z, h, n: (N.GRID_H3, 5, 1, N.ptr(z), N.ptr(z), N.ptr(z), N.ptr(np.zeros(2)), ctypes.byref(h))),
+    ("mosaic_chips_kring", lambda z, h, n: (N.GRID_H3, 5, 0, None, None, None, 1, 1, 0, ctypes.byref(h))),
+    ("mosaic_st_distance", lambda z, h, n: (None, None, None, None, 0, None, None)),
+    ("mosaic_ring_neighbours", lambda z, h, n: (None, None, None, None, None, 0, 0, ctypes.byref(h))),
+    ("mosaic_tessellate_lines_gpu", lambda z, h, n: (N.GRID_H3, 5, 0, N.ptr(z), N.ptr(z), None, 0, ctypes.byref(h))),
+    ("mosaic_line_intersects_aggregate", lambda z, h, n: (None, None, None, None, None, 0, ctypes.byref(n))),
+    ("mosaic_line_intersection_aggregate", lambda z, h, n: (None, None, None, None, None, 0, ctypes.byref(n))),
+    ("mosaic_st_intersects", lambda z, h, n: (None, None, None, None, 0, None, None)),
+]
+
+
+@pytest.mark.parametrize("name,args", _NULL_CTX_CALLS, ids=[c[0] for c in _NULL_CTX_CALLS])
+def test_feature_entry_points_refuse_a_null_context(name, args):
+    """polyfill.hip, geom_kring.hip, st_distance.hip, ring_neighbours.hip, line_fill.hip, line_join.hip,
+    line_clip.hip and st_intersects.hip share one error return (fail.h): a call without a context is
+    MOSAIC_E_ARG with a message of its own, and it returns before any device work (no GPU needed)."""
+    lib = N.lib()
+    out = ctypes.c_int(0)
+    assert lib.mosaic_resolution(N.GRID_H3, 16, ctypes.byref(out)) == N.MOSAIC_E_RES
+    before = lib.mosaic_last_error()
+    rc = getattr(lib, name)(None, *args(np.zeros(2, np.int64), ctypes.c_void_p(), ctypes.c_int64(0)))
+    assert rc == N.MOSAIC_E_ARG
+    msg = lib.mosaic_last_error()
+    assert msg and msg != before
