@@ -737,6 +737,27 @@ int mosaic_st_intersects(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic
 /* the calling thread's last mosaic_st_intersects: pairs ended in the plan kernel (null, row-path, empty
  * or box-disjoint), pairs served by one lane, pairs served by a workgroup (any may be null) */
 int mosaic_st_intersects_last_split(int64_t* ended_in_plan, int64_t* one_lane, int64_t* workgroup);
+/* The measures of one geometry per row (ST_Area, ST_Length = ST_Perimeter, ST_Centroid, ST_NumPoints,
+ * ST_XMin .. ST_YMax -> MosaicGeometryJTS -> JTS 1.19 getArea / getLength / getCentroid /
+ * getNumPoints): output row i describes geoms[rows[i]], rows == NULL: row i (n <= the column's rows).
+ * Every output pointer is nullable and only the non-null ones are computed; each may be a host or a
+ * device pointer, as may rows.  The values are those of the sequential definition in
+ * mosaic_amd/csrc/st_measures.h, bit for bit: area = sum over polygon parts of |shell| - |holes|
+ * (lines and points 0.0); length = every ring's and component line's length (a polygon's perimeter;
+ * points 0.0); centroid = JTS Centroid (area part, else line part, else the mean of the points);
+ * numpoints = the stored vertex count (a closed ring counts its closing vertex); the bounds = the
+ * geometry's envelope.  A geometry without a vertex: area 0.0, length 0.0, numpoints 0, centroid and
+ * bounds NaN (the reference throws on the bounds).  status[i]: MOSAIC_ROW_OK; MOSAIC_ROW_NULL and
+ * MOSAIC_ROW_PATH rows give NaN and numpoints 0.  Line rows are served in a column built with
+ * MOSAIC_GEOMS_LINES.  A row index out of range: MOSAIC_E_ARG, nothing written; so is a column whose
+ * sizes pass the store's 32-bit offsets.  Options: "meas_wave_min" (stored vertices from which a row
+ * takes a wave instead of one lane, default 128) and "meas_tile" (segments per LDS tile of the wave
+ * kernel, [1, 256], default 256); neither changes a bit of the result. */
+int mosaic_st_measures(mosaic_ctx* ctx, const mosaic_geoms* geoms, const int64_t* rows /*nullable*/, int64_t n,
+                       double* area, double* length, double* centroid_x, double* centroid_y, int64_t* numpoints,
+                       double* xmin, double* ymin, double* xmax, double* ymax, int32_t* status);
+/* the calling thread's last mosaic_st_measures: rows served by one lane, rows served by a wave (either may be null) */
+int mosaic_st_measures_last_split(int64_t* one_lane, int64_t* wave);
 
 /* ---- GridRingNeighbours: one iteration of the KNN model (models/knn/GridRingNeighbours.scala:121-160) ---- */
 /* The candidates' chips as a map from a cell to its sorted, distinct candidate rows: built once per chip

@@ -6,7 +6,8 @@ include/mosaic_hip.h; this package is the host-side mirror of the reference's fu
 from ._native import IllegalStateException, MosaicError, NativeUnavailable  # noqa: F401
 from .context import (BNGIndexSystem, ChipTable, GeometryTable, H3IndexSystem, LineChipTable, MosaicContext,  # noqa: F401
                       RowPathRequired, line_intersection_aggregate_host, line_intersects_aggregate_host)
+from .analyzer import MosaicAnalyzer, NotEnoughGeometries  # noqa: F401
 from .knn import CellIndex, SpatialKNN  # noqa: F401
 
-__all__ = ["MosaicContext", "ChipTable", "LineChipTable", "line_intersects_aggregate_host", "line_intersection_aggregate_host", "GeometryTable", "CellIndex", "SpatialKNN", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
+__all__ = ["MosaicContext", "MosaicAnalyzer", "NotEnoughGeometries", "ChipTable", "LineChipTable", "line_intersects_aggregate_host", "line_intersection_aggregate_host", "GeometryTable", "CellIndex", "SpatialKNN", "H3IndexSystem", "BNGIndexSystem", "IllegalStateException",
            "MosaicError", "NativeUnavailable"]

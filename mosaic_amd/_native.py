@@ -55,6 +55,7 @@ EXPORTS = [
     "mosaic_line_intersection_aggregate", "mosaic_line_intersection_aggregate_geometry",
     "mosaic_line_intersection_last", "mosaic_line_intersection_aggregate_host",
     "mosaic_st_intersects", "mosaic_st_intersects_last_split",
+    "mosaic_st_measures", "mosaic_st_measures_last_split",
 ]
 
 GEOM_WKB = 0
@@ -191,6 +192,8 @@ def lib():
         "mosaic_st_distance": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
         "mosaic_st_intersects": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
         "mosaic_st_intersects_last_split": ([ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "mosaic_st_measures": ([vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mosaic_st_measures_last_split": ([ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_cell_index_create": ([vp, i64, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_cell_index_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_cell_index_destroy": ([vp], i32),

@@ -957,6 +957,133 @@ class MosaicContext:
         res = self._pair_call("st_intersects", N.lib().mosaic_st_intersects, np.uint8, left, right, pairs, return_status)
         return (res[0].astype(bool), res[1]) if return_status else res.astype(bool)
 
+    # ---- one geometry per row: area, length, centroid, numpoints, bounds ----
+    MEASURES = ("area", "length", "centroid", "numpoints", "xmin", "ymin", "xmax", "ymax")
+
+    @classmethod
+    def _measure_names(cls, what):
+        """``what`` as a tuple of distinct names of MEASURES ("perimeter" is "length"); ValueError otherwise"""
+        if isinstance(what, str):
+            what = (what,)
+        names = []
+        for w in what:
+            if not isinstance(w, str):
+                raise ValueError(f"st_measures: what holds {w!r}, not a name")
+            w = "length" if w == "perimeter" else w
+            if w not in cls.MEASURES:
+                raise ValueError(f"st_measures: unknown measure {w!r} (one of {', '.join(cls.MEASURES)}, perimeter)")
+            if w not in names:
+                names.append(w)
+        if not names:
+            raise ValueError("st_measures: what is empty")
+        return tuple(names)
+
+    def st_measures(self, geoms, what=MEASURES, rows=None, return_status=False, lines=False):
+        """Several measures of one geometry per row in one call (mosaic_st_measures): ``what`` names
+        any of "area", "length" (or "perimeter"), "centroid", "numpoints", "xmin", "ymin", "xmax",
+        "ymax"; only those are computed.  Returns a dict from the name to a float64 array (int64 for
+        numpoints; "centroid": the pair ``(x, y)``) -- the bits of the sequential definition in
+        mosaic_amd/csrc/st_measures.h (JTS 1.19 getArea / getLength / getCentroid / getNumPoints and
+        the envelope).  An empty geometry has area 0.0, length 0.0, numpoints 0 and NaN centroid and
+        bounds; null rows give NaN (numpoints 0).
+
+        ``geoms``: a ``GeometryTable``, or anything ``geometry_table`` accepts (the table is then
+        built with ``lines`` and closed inside the call).  LineString / MultiLineString rows are served
+        by a LineSet or a table built with ``lines=True``, as for ``st_distance``.  ``rows``: the rows
+        to measure, in that order (host array or device tensor); None = every row.  Rows left to the
+        row path raise ``RowPathRequired`` unless return_status, which adds the "status" array
+        (ROW_OK / ROW_NULL / ROW_PATH; NaN on row-path rows too)."""
+        names = self._measure_names(what)
+        own = None
+        try:
+            table = geoms
+            if not isinstance(geoms, GeometryTable):
+                table = own = self.geometry_table(geoms, lines=lines)
+            if rows is None:
+                n = len(table)
+            else:
+                if _is_torch(rows):
+                    import torch
+
+                    rows = rows.to(torch.int64).contiguous()
+                    self._order(rows)
+                else:
+                    rows = np.ascontiguousarray(rows, np.int64)
+                n = len(rows)
+            size = max(n, 1)
+            bufs = {w: np.zeros(size) for w in names if w not in ("centroid", "numpoints")}
+            if "centroid" in names:
+                bufs["cx"], bufs["cy"] = np.zeros(size), np.zeros(size)
+            if "numpoints" in names:
+                bufs["numpoints"] = np.zeros(size, np.int64)
+            status = np.zeros(size, np.int32)
+            order = ("area", "length", "cx", "cy", "numpoints", "xmin", "ymin", "xmax", "ymax")
+            N.check(N.lib().mosaic_st_measures(self.handle, table.handle, N.ptr(rows), n, *[N.ptr(bufs.get(k)) for k in order],
+                                               N.ptr(status)))
+        finally:
+            if own is not None:
+                own.close()
+        status = status[:n]
+        out = {w: (bufs["cx"][:n], bufs["cy"][:n]) if w == "centroid" else bufs[w][:n] for w in names}
+        if return_status:
+            out["status"] = status
+            return out
+        path = np.flatnonzero(status == N.ROW_PATH)
+        if len(path):
+            raise RowPathRequired(path)
+        return out
+
+    def _measure(self, name, geoms, return_status, lines):
+        out = self.st_measures(geoms, (name,), return_status=return_status, lines=lines)
+        return (out[name], out["status"]) if return_status else out[name]
+
+    def st_area(self, geoms, return_status=False, lines=False):
+        """st_area(geom) (ST_Area.scala -> MosaicGeometryJTS.getArea -> JTS Geometry.getArea): per
+        polygon part |shell| minus its |holes| by Area.ofRingSigned, summed over the parts; 0.0 for
+        lines, points and empty geometries.  Arguments and row handling as for ``st_measures``."""
+        return self._measure("area", geoms, return_status, lines)
+
+    def st_length(self, geoms, return_status=False, lines=False):
+        """st_length(geom) (ST_Length.scala -> JTS Geometry.getLength): the length of every component
+        line and of every polygon ring, holes included (the perimeter); 0.0 for points."""
+        return self._measure("length", geoms, return_status, lines)
+
+    def st_perimeter(self, geoms, return_status=False, lines=False):
+        """st_perimeter(geom): the reference registers ST_Length under this name too (MosaicContext.scala:488)."""
+        return self._measure("length", geoms, return_status, lines)
+
+    def st_centroid(self, geoms, return_status=False, lines=False):
+        """st_centroid(geom) / st_centroid2D (ST_Centroid.scala -> JTS Geometry.getCentroid) as ``(x, y)``:
+        JTS Centroid's area part; without area its line part; without length the mean of the points;
+        (NaN, NaN) for an empty geometry."""
+        return self._measure("centroid", geoms, return_status, lines)
+
+    def st_numpoints(self, geoms, return_status=False, lines=False):
+        """st_numpoints(geom) (JTS Geometry.getNumPoints): a closed ring counts its closing vertex."""
+        return self._measure("numpoints", geoms, return_status, lines)
+
+    def st_xmin(self, geoms, return_status=False, lines=False):
+        """st_xmin(geom): the envelope's smallest x; NaN for an empty geometry (the reference throws)."""
+        return self._measure("xmin", geoms, return_status, lines)
+
+    def st_xmax(self, geoms, return_status=False, lines=False):
+        """st_xmax(geom); see ``st_xmin``."""
+        return self._measure("xmax", geoms, return_status, lines)
+
+    def st_ymin(self, geoms, return_status=False, lines=False):
+        """st_ymin(geom); see ``st_xmin``."""
+        return self._measure("ymin", geoms, return_status, lines)
+
+    def st_ymax(self, geoms, return_status=False, lines=False):
+        """st_ymax(geom); see ``st_xmin``."""
+        return self._measure("ymax", geoms, return_status, lines)
+
+    def st_measures_last_split(self):
+        """(rows served by one lane, rows served by a wave) of this thread's last ``st_measures``"""
+        a, b = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        N.check(N.lib().mosaic_st_measures_last_split(ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ---- the KNN model (mosaic_amd/knn.py) ----
     def cell_index(self, chips):
         """A ``CellIndex``: the candidates' chips as a device-resident map from a cell to its candidate

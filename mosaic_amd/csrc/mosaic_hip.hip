@@ -2036,6 +2036,10 @@ struct Options {
     int dist_tile = 16;
     int64_t dist_small_work = 512;
     int dist_prune = 1;
+    // st_measures (st_measures.hip): segments per LDS tile of k_meas_wave, and the stored vertex count
+    // from which a row takes a wave instead of one lane
+    int meas_tile = 256;
+    int64_t meas_wave_min = 128;
 };
 
 // Execution state of one calling thread on one context: its HIP stream (created on first use, or
@@ -2414,6 +2418,15 @@ int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int
     return MOSAIC_OK;
 }
 
+// the "meas_tile" / "meas_wave_min" options, for st_measures.hip
+int mosaic_ctx_meas_options(mosaic_ctx* ctx, int* tile, int64_t* wave_min) {
+    if (!ctx) return fail(MOSAIC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *tile = ctx->opt.meas_tile;
+    *wave_min = ctx->opt.meas_wave_min;
+    return MOSAIC_OK;
+}
+
 // what k_isect_agg reads from a chip table, for line_join.hip
 int mosaic_chips_join_view(const mosaic_chips* chips, ChipsJoinView* out) {
     if (!chips || !out) return fail(MOSAIC_E_ARG, "null chip table");
@@ -2733,6 +2746,12 @@ int mosaic_set_option(mosaic_ctx* ctx, const char* key, int64_t v) {
         o.dist_small_work = v;
     } else if (k == "dist_prune") {
         o.dist_prune = v != 0;
+    } else if (k == "meas_tile") {
+        if (v < 1 || v > 256) return fail(MOSAIC_E_ARG, "meas_tile must be in [1, 256]");
+        o.meas_tile = (int)v;
+    } else if (k == "meas_wave_min") {
+        if (v < 0) return fail(MOSAIC_E_ARG, "meas_wave_min must be >= 0");
+        o.meas_wave_min = v;
     } else {
         return fail(MOSAIC_E_ARG, "unknown option " + k);
     }
