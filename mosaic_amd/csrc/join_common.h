@@ -171,6 +171,34 @@ __device__ inline void stage_flush(const JoinArgs& a, uint32_t* wq, uint32_t& wn
     __builtin_amdgcn_wave_barrier();
     wn = 0;
 }
+// The same stage with two-word entries (stream_kernel_h3 queue2: the row, then what the stream kernel's
+// lookup found for k_join_leaf): entry e at words 2 e, 2 e + 1, kStageWords / 2 = 64 entries.  A push
+// adds up to 64, so the stage is flushed BEFORE a push of n rows it has no room for (stage_flush2
+// with min_rows = 65 - n) instead of after; k_join_stream_cpt, whose stage runs on into the wave's
+// compaction buffer, flushes after the push like the one-word stage.  The global queue write stays
+// one atomic per flush.
+__device__ inline void stage_push2(uint32_t* wq, uint32_t& wn, bool mixed, uint32_t rowoff, uint32_t info,
+                                   unsigned long long lt_mask) {
+    const unsigned long long mm = __ballot(mixed);
+    if (mixed) {
+        const uint32_t e = wn + (uint32_t)__popcll(mm & lt_mask);
+        wq[2u * e] = rowoff;
+        wq[2u * e + 1u] = info;
+    }
+    wn += (uint32_t)__popcll(mm);
+}
+__device__ inline void stage_flush2(const JoinArgs& a, uint32_t* wq, uint32_t& wn, int lane, uint32_t min_rows) {
+    if (wn < min_rows || wn == 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(a.mixq_count, (unsigned long long)wn);
+    base = __shfl(base, 0, 64);
+    for (uint32_t k = (uint32_t)lane; k < 2u * wn; k += 64) a.mixq[2u * base + k] = wq[k];
+    __builtin_amdgcn_wave_barrier();
+    wn = 0;
+}
 
 struct StreamArgs {
     double x0, y0, sxC, syC;  // fine-cell coordinates g = (x - x0) sxC, (y - y0) syC (C per sub-block)
@@ -198,7 +226,7 @@ struct StreamArgs {
     const tiles::LineRec* llines;
 };
 // per-wave mixed-row stage of the stream kernels (words): rows are appended one slot (<= 64 rows)
-// at a time and flushed at >= 64
+// at a time and flushed at >= 64 (two-word entries: 64 of them, flushed before a slot that would not fit)
 static const int kStageWords = 128;
 // k_join_stream_cpt's per-wave compaction buffer (words): 64 slots x 3 words
 static const int kCptBufWords = 192;
@@ -295,7 +323,10 @@ struct BngStreamArgs {
 
 // The stream kernels (join_stream.hip), by template arguments: the host picks one and launches it
 // with hipLaunchKernel.  pipe: k_join_stream_pipe (needs vec); else k_join_stream<lds, pairs, vec>.
-const void* stream_kernel_h3(int pipe, bool lds, bool pairs, bool vec);
+// queue2 (k_join_leaf follows; n_tiles <= 65536): mixed-queue entries are two words, the row
+// (- row_lo) and tile << 16 | code -- the leaf code of a leaf-block row, kMixed for every other row
+// (line sub-block bands, mixed quad / sub-block entries, non-finite rows); else the row alone.
+const void* stream_kernel_h3(int pipe, bool lds, bool pairs, bool vec, bool queue2);
 // k_join_leaf<lds, pairs> (join_stream.hip): the mixed queue's leaf-line rows, before k_join_mixed
 const void* leaf_kernel(bool lds, bool pairs);
 const void* stream_kernel_bng(bool lds, bool pairs, bool vec, bool cpt);  // cpt: k_join_stream_bng_cpt (needs vec)

@@ -18,7 +18,7 @@
 // 128 + 2l, 129 + 2l, so each 16-byte coordinate load instruction reads 1 KiB contiguous.  The
 // next iteration's coordinates are loaded after this iteration's gathers are issued (vector-memory
 // returns retire in order: waiting for the gathers does not wait for them).
-template <bool LDS_COUNTS, bool PAIRS, bool VEC>
+template <bool LDS_COUNTS, bool PAIRS, bool VEC, bool Q2>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) k_join_stream(JoinArgs a, StreamArgs s) {
     extern __shared__ unsigned int lds[];
     const int nwaves = (int)(blockDim.x >> 6);
@@ -152,13 +152,31 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
             for (int k = 0; k < 4; k++) {
                 const bool m = code[k] == tiles::kMixed;
                 const unsigned long long mm = __ballot(m);
-                if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row_of(w0, k) - a.row_lo);
-                wn += (uint32_t)__popcll(mm);
-                stage_flush(a, wq, wn, lane, 64);  // one atomic per >= 64 rows; the stage holds < 128
+                if (Q2) {
+                    // k_join_leaf's entry: the gathered leaf code of a leaf-block row.  Its line offsets
+                    // are fixed-point (tiles::raster_code_fixed), whose rounding can put a point on a
+                    // cell edge into the neighbour of the cell looked up here: such a row, like every
+                    // other, goes on to k_join_mixed (kMixed).  Coordinates re-read: rare rows, and the
+                    // loop carries no more live registers for them
+                    uint32_t lc = tiles::kMixed;
+                    if (m && fin[k] && blk[k] && !line[k]) {
+                        const int64_t r = row_of(w0, k);
+                        const uint32_t gix = min(tiles::fix_cvt(fma(a.x[r], s.sxF, s.gx0F)), (uint32_t)s.gxmaxF);
+                        const uint32_t giy = min(tiles::fix_cvt(fma(a.y[r], s.syF, s.gy0F)), (uint32_t)s.gymaxF);
+                        if ((gix >> tiles::kFixBits) == ixC[k] && (giy >> tiles::kFixBits) == iyC[k]) lc = leaf[k];
+                    }
+                    stage_flush2(a, wq, wn, lane, 65u - (uint32_t)__popcll(mm));
+                    stage_push2(wq, wn, m, (uint32_t)(row_of(w0, k) - a.row_lo), (ta[k] << 16) | lc, lt_mask);
+                } else {
+                    if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row_of(w0, k) - a.row_lo);
+                    wn += (uint32_t)__popcll(mm);
+                    stage_flush(a, wq, wn, lane, 64);  // one atomic per >= 64 rows; the stage holds < 128
+                }
             }
         }
     }
-    stage_flush(a, wq, wn, lane, 1);
+    if (Q2) stage_flush2(a, wq, wn, lane, 1);
+    else stage_flush(a, wq, wn, lane, 1);
     if (LDS_COUNTS) {
         __syncthreads();
         for (int k = threadIdx.x; k < a.n_polygons; k += blockDim.x)
@@ -217,7 +235,7 @@ static_assert(tiles::kMaxRasterKeys + 1 < 0x7fff, "key codes stay below kPipeNon
 // stage B -> D marker of a row in a line sub-block (above every code)
 static const uint32_t kPipeLine = 0x10000u;
 
-template <bool LDS_COUNTS, bool PAIRS>
+template <bool LDS_COUNTS, bool PAIRS, bool Q2>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) k_join_stream_pipe(JoinArgs a, StreamArgs s) {
     extern __shared__ unsigned int lds[];
     const int nwaves = (int)(blockDim.x >> 6);
@@ -325,13 +343,28 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
         }
         const uint32_t cmax = max(max(code[0], code[1]), max(code[2], code[3]));
         if (__ballot(cmax >= kPipeNonFinite)) {
+            if (Q2) {
+                // k_join_leaf's entries: the tile and the answer -- the leaf code (leaf-block rows) or
+                // kMixed -- of all four rows first, so that only they are held across a flush
+                constexpr int SH = tiles::kFixBits;
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const bool m = code[k] >= kPipeNonFinite;
-                const unsigned long long mm = __ballot(m);
-                if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row_of(wb, k) - a.row_lo);
-                wn += (uint32_t)__popcll(mm);
-                stage_flush(a, wq, wn, lane, 64);  // the stage holds < 128
+                for (int k = 0; k < 4; k++)
+                    code[k] |= (__umul24(g.gy[k] >> (s.tsh + SH), (uint32_t)s.tnx) + (g.gx[k] >> (s.tsh + SH))) << 16;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const bool m = (code[k] & 0xffffu) >= kPipeNonFinite;
+                    stage_flush2(a, wq, wn, lane, 65u - (uint32_t)__popcll(__ballot(m)));
+                    stage_push2(wq, wn, m, (uint32_t)(row_of(wb, k) - a.row_lo), code[k], lt_mask);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const bool m = code[k] >= kPipeNonFinite;
+                    const unsigned long long mm = __ballot(m);
+                    if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row_of(wb, k) - a.row_lo);
+                    wn += (uint32_t)__popcll(mm);
+                    stage_flush(a, wq, wn, lane, 64);  // the stage holds < 128
+                }
             }
         }
     };
@@ -405,7 +438,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
         stage_b(g);
         stage_d(g, wt);
     }
-    stage_flush(a, wq, wn, lane, 1);
+    if (Q2) stage_flush2(a, wq, wn, lane, 1);
+    else stage_flush(a, wq, wn, lane, 1);
     if (LDS_COUNTS) {
         __syncthreads();
         for (int k = threadIdx.x; k < a.n_polygons; k += blockDim.x)
@@ -435,22 +469,24 @@ struct CptSet {
     uint32_t a;     // ix low bits | source lane << 24 | row slot k << 30
     uint32_t b;     // iy low bits
     uint32_t c;     // quad entry | tile index << 16
-    uint32_t code;  // A -> B: gathered sub-block entry; B -> D: the answer, 0 for leaf rows, or kPipeLine
-    uint32_t leaf;  // gathered leaf code
+    uint32_t code;  // A -> B: gathered sub-block entry; B -> D: the answer (0 for leaf and line rows) | tile index << 16
+    uint32_t leaf;  // gathered leaf code, or kPipeLine for a line row
     v4u lrec;       // gathered line record
 };
 
-template <bool LDS_COUNTS, bool PAIRS>
+template <bool LDS_COUNTS, bool PAIRS, bool Q2>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) k_join_stream_cpt(JoinArgs a, StreamArgs s) {
     extern __shared__ unsigned int lds[];
     const int nwaves = (int)(blockDim.x >> 6);
     const int ncw = LDS_COUNTS ? a.n_polygons + 64 : 0;
     uint32_t* stage = lds + ncw;
-    // per-wave compaction buffers: 64 slots x 3 words, structure of arrays
-    uint32_t* cbuf_all = stage + nwaves * s.stage_words;
+    // per wave: the mixed-row stage, then the compaction buffer (64 slots x 3 words, structure of
+    // arrays) -- adjacent, so that a push of two-word entries (Q2) can run on into the buffer,
+    // which is free outside gather_set, until the flush that follows it
+    const int wave_words = s.stage_words + kCptBufWords;
     // tile bases in LDS (s.tb_lds), or gathered beside the sub-block entry (large tile grids: their
     // LDS goes to a finer quad level instead)
-    uint32_t* tb = cbuf_all + nwaves * kCptBufWords;
+    uint32_t* tb = stage + nwaves * wave_words;
     uint32_t* quadw = tb + (s.tb_lds ? s.n_tiles : 0);
     const uint16_t* quad = (const uint16_t*)quadw;
     uint32_t* qmask = quadw + s.n_quad_words;
@@ -467,8 +503,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
     const int lane = (int)(threadIdx.x & 63);
     const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint32_t* wq = stage + wave * s.stage_words;
-    uint32_t* cbuf = cbuf_all + wave * kCptBufWords;
+    uint32_t* wq = stage + wave * wave_words;
+    uint32_t* cbuf = wq + s.stage_words;
     uint32_t wn = 0;
     constexpr int F = tiles::kFixBits;
     const uint32_t cs = (uint32_t)s.cs, qs = (uint32_t)s.qs;
@@ -525,9 +561,14 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
 #endif
         if (MOSAIC_ABL_GATHER_HIT & 2) loff &= 0xffeu;
 #endif
-        z.leaf = gather_b16<0>(rblk, blk && !line, loff);
+        // for stage D: z.leaf is kPipeLine for a line row, else the gathered leaf code (0: no gather)
+        // to OR with z.code's low half (0 for leaf rows); z.code's high half keeps the tile for the
+        // mixed queue's entry (z.c is dead from here on: no register is held for it)
+        uint32_t lf16 = line ? kPipeLine : 0u;
+        if (blk && !line) lf16 = __builtin_amdgcn_raw_buffer_load_b16(rblk, loff, 0, 0);
+        z.leaf = lf16;
         z.lrec = gather_b128<0>(rblk, line, roff);
-        z.code = line ? kPipeLine : (blk ? 0u : c);
+        z.code = (z.c & 0xffff0000u) | (blk ? 0u : c);
     };
     // D: answers of the set's rows (group base wb)
     auto set_d = [&](CptSet& z, int64_t wb) {
@@ -535,7 +576,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
 #ifdef MOSAIC_ABL_GATHER_HIT  // (measurement builds) wait for the gathers, then answer key 0
         __asm__ volatile("" ::"v"(z.lrec.x), "v"(z.lrec.y), "v"(z.lrec.z), "v"(z.lrec.w), "v"(z.leaf));
         if (MOSAIC_ABL_GATHER_HIT & 9) z.lrec = v4u{0u, 0u, __float_as_uint(2.0f), 0x00010001u};
-        if (MOSAIC_ABL_GATHER_HIT & 10) z.leaf = z.code == kPipeLine ? z.leaf : 1u;
+        if (MOSAIC_ABL_GATHER_HIT & 10) z.leaf = z.leaf == kPipeLine ? z.leaf : 1u;
 #endif
         const float u = (float)__builtin_amdgcn_ubfe(z.a, 0u, fb) * (1.0f / (float)(1 << F));
         const float v = (float)__builtin_amdgcn_ubfe(z.b, 0u, fb) * (1.0f / (float)(1 << F));
@@ -543,16 +584,24 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
         const uint32_t pos = z.lrec.w & 0xffffu, neg = z.lrec.w >> 16;
         uint32_t lc = sv >= 1.0f ? pos : (uint32_t)tiles::kMixed;
         lc = sv <= -1.0f ? neg : lc;
-        const uint32_t code = z.code == kPipeLine ? lc : (z.code | z.leaf);
+        const uint32_t code = z.leaf == kPipeLine ? lc : ((z.code & 0xffffu) | z.leaf);
         const uint32_t src = (z.a >> 24) & 63u, k = z.a >> 30;
         const int64_t row = wb + (int64_t)((k >> 1) * 128u + 2u * src + (k & 1u));
         answer(code, row);
         const bool m = code >= kPipeNonFinite;
         if (__ballot(m)) {
             const unsigned long long mm = __ballot(m);
-            if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row - a.row_lo);
-            wn += (uint32_t)__popcll(mm);
-            stage_flush(a, wq, wn, lane, 64);  // the stage holds < 128
+            if (Q2) {
+                // k_join_leaf's entry: the set's tile and the answer -- the leaf code (leaf-block rows) or
+                // kMixed.  Up to 63 + 64 entries before the flush: the last run on into cbuf
+                static_assert(kStageWords + kCptBufWords >= 2 * 127, "a full push fits behind a stage that was not flushed");
+                stage_push2(wq, wn, m, (uint32_t)(row - a.row_lo), (z.code & 0xffff0000u) | code, lt_mask);
+                stage_flush2(a, wq, wn, lane, 64);
+            } else {
+                if (m) wq[wn + __popcll(mm & lt_mask)] = (uint32_t)(row - a.row_lo);
+                wn += (uint32_t)__popcll(mm);
+                stage_flush(a, wq, wn, lane, 64);  // the stage holds < 128
+            }
         }
     };
     // --- stage A of a group: LDS levels, resolved rows answered, pending rows compacted into z (the
@@ -695,7 +744,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
             set_d(z2, wt);
         }
     }
-    stage_flush(a, wq, wn, lane, 1);
+    if (Q2) stage_flush2(a, wq, wn, lane, 1);
+    else stage_flush(a, wq, wn, lane, 1);
     if (LDS_COUNTS) {
         __syncthreads();
         for (int k = threadIdx.x; k < a.n_polygons; k += blockDim.x)
@@ -1141,10 +1191,12 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
 // ---- k_join_leaf: the mixed queue's rows whose leaf cell is a leaf line (tiles.h leaf_is_line: the
 // cell is split by one straight chip edge) are answered from the line record; the others -- the
 // line's band, mixed leaf cells, line sub-blocks' bands, non-finite rows -- move to queue q2, which
-// k_join_mixed then takes.  One lane per row: tiles::raster_code_fixed's chain from global memory
-// (quad level, quad record, compact sub-block entry, tile base, leaf code, line record), the same
-// fine cell and line offsets as the stream kernels.  ~95 % of NYC res-9 mixed leaf cells are leaf
-// lines (tools/raster_stats.cpp), so the mixed kernel's H3 cell + chip loop runs on ~1/5 of the rows.
+// k_join_mixed then takes.  One lane per row.  The stream kernel queued the row with its tile and the
+// leaf code it gathered (two-word entries, stream_kernel_h3 queue2), so the raster is not walked
+// again: a leaf-line row loads its coordinates beside tile_lbase[tile] -> llines[...] and takes
+// tiles::raster_code_fixed's line offsets; every other row goes to q2 on the entry alone (one-word
+// entries there).  ~95 % of NYC res-9 mixed leaf cells are leaf lines (tools/raster_stats.cpp), so
+// the mixed kernel's H3 cell + chip loop runs on ~1/5 of the rows.
 template <bool LDS_COUNTS, bool PAIRS>
 __global__ void __launch_bounds__(256) k_join_leaf(JoinArgs a, StreamArgs s, uint32_t* q2, unsigned long long* q2_count) {
     extern __shared__ unsigned int lds[];
@@ -1162,45 +1214,30 @@ __global__ void __launch_bounds__(256) k_join_leaf(JoinArgs a, StreamArgs s, uin
     constexpr int F = tiles::kFixBits;
     const int lane = (int)(threadIdx.x & 63);
     const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
-    const uint16_t* quad = (const uint16_t*)s.quad;
-    const uint32_t* qmask = s.qrec;
-    const uint16_t* qcode = (const uint16_t*)(s.qrec + 2 * s.n_qrec);
-    const uint32_t cs = (uint32_t)s.cs, qs = (uint32_t)s.qs, cm = (1u << cs) - 1u, qm = (1u << qs) - 1u;
+    const uint2* __restrict__ mixq2 = (const uint2*)a.mixq;
+    const uint32_t fm = (1u << ((uint32_t)s.cs + F)) - 1u;
+    const float sc = 1.0f / (float)(1 << F);
     const unsigned long long total = *a.mixq_count;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     // wave-uniform loop (the q2 append is a wave ballot)
     for (unsigned long long t0 = (unsigned long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); t0 < total; t0 += stride) {
         const unsigned long long t = t0 + (unsigned long long)lane;
         const bool live = t < total;
-        const uint32_t off = live ? a.mixq[t] : 0u;
+        uint2 e = {0u, (uint32_t)tiles::kMixed};
+        if (live) e = mixq2[t];
+        const uint32_t off = e.x, lc = e.y & 0xffffu;
         const int64_t row = a.row_lo + (int64_t)off;
         uint32_t code = tiles::kMixed;
-        if (live) {
+        if (live && tiles::leaf_is_line(lc)) {
+            // the coordinates and the tile's first line: independent loads, in flight together
             const double x = a.x[row], y = a.y[row];
-            if (isfinite(x + y)) {
-                const uint32_t gix = min(tiles::fix_cvt(fma(x, s.sxF, s.gx0F)), (uint32_t)s.gxmaxF);
-                const uint32_t giy = min(tiles::fix_cvt(fma(y, s.syF, s.gy0F)), (uint32_t)s.gymaxF);
-                const uint32_t ixC = gix >> F, iyC = giy >> F, ix = ixC >> cs, iy = iyC >> cs;
-                const uint32_t q = quad_lookup<F>(s, quad, qmask, qcode, gix, giy);
-                const uint32_t e = q < 0x8000u ? q : s.csub[((q & 0x7fffu) << (2 * qs)) + (((iy & qm) << qs) | (ix & qm))];
-                code = e;
-                if (tiles::sub_is_block(e) && !(e & tiles::kLineBit)) {
-                    const uint32_t tile = (iyC >> s.tsh) * (uint32_t)s.tnx + (ixC >> s.tsh);
-                    const uint32_t base = s.tile_base[tile];
-                    const uint32_t lc = s.blocks[base + ((e & 0x3fffu) << (2 * cs)) + (((iyC & cm) << cs) | (ixC & cm))];
-                    code = lc;
-                    if (tiles::leaf_is_line(lc)) {
-                        const tiles::LineRec lr = s.llines[s.tile_lbase[tile] + (lc & 0x3fffu)];
-                        const uint32_t fm = (1u << (cs + F)) - 1u;
-                        const float sc = 1.0f / (float)(1 << F);
-                        code = tiles::line_code(lr, (float)(gix & fm) * sc, (float)(giy & fm) * sc);
-                    }
-                } else if (tiles::sub_is_block(e)) {
-                    code = tiles::kMixed;  // a line sub-block's band (the stream kernel's answer)
-                }
-            }
+            const uint32_t lbase = s.tile_lbase[e.y >> 16];
+            const tiles::LineRec lr = s.llines[lbase + (lc & 0x3fffu)];
+            const uint32_t gix = min(tiles::fix_cvt(fma(x, s.sxF, s.gx0F)), (uint32_t)s.gxmaxF);
+            const uint32_t giy = min(tiles::fix_cvt(fma(y, s.syF, s.gy0F)), (uint32_t)s.gymaxF);
+            code = tiles::line_code(lr, (float)(gix & fm) * sc, (float)(giy & fm) * sc);
         }
-        const bool keep = live && code >= 0x8000u;  // kMixed (or a code the chain cannot decide)
+        const bool keep = live && code >= 0x8000u;  // kMixed: the line's band, or a row without a leaf line
         if (live && !keep && code != 0u) {
             if (LDS_COUNTS && !PAIRS) atomicAdd(&lds[code - 1u], 1u);
             else emit_hit<LDS_COUNTS, PAIRS>(a, row, code - 1u, lds);
@@ -1222,20 +1259,24 @@ const void* leaf_kernel(bool lds, bool pairs) {
     return (const void*)k_join_leaf<false, false>;
 }
 
-const void* stream_kernel_h3(int pipe, bool lds, bool pairs, bool vec) {
+template <bool Q2>
+static const void* stream_kernel_h3_q(int pipe, bool lds, bool pairs, bool vec) {
     if (pipe == 2 && vec) {
-        if (pairs) return (const void*)k_join_stream_cpt<false, true>;
-        if (lds) return (const void*)k_join_stream_cpt<true, false>;
-        return (const void*)k_join_stream_cpt<false, false>;
+        if (pairs) return (const void*)k_join_stream_cpt<false, true, Q2>;
+        if (lds) return (const void*)k_join_stream_cpt<true, false, Q2>;
+        return (const void*)k_join_stream_cpt<false, false, Q2>;
     }
     if (pipe && vec) {
-        if (pairs) return (const void*)k_join_stream_pipe<false, true>;
-        if (lds) return (const void*)k_join_stream_pipe<true, false>;
-        return (const void*)k_join_stream_pipe<false, false>;
+        if (pairs) return (const void*)k_join_stream_pipe<false, true, Q2>;
+        if (lds) return (const void*)k_join_stream_pipe<true, false, Q2>;
+        return (const void*)k_join_stream_pipe<false, false, Q2>;
     }
-    if (pairs) return vec ? (const void*)k_join_stream<false, true, true> : (const void*)k_join_stream<false, true, false>;
-    if (lds) return vec ? (const void*)k_join_stream<true, false, true> : (const void*)k_join_stream<true, false, false>;
-    return vec ? (const void*)k_join_stream<false, false, true> : (const void*)k_join_stream<false, false, false>;
+    if (pairs) return vec ? (const void*)k_join_stream<false, true, true, Q2> : (const void*)k_join_stream<false, true, false, Q2>;
+    if (lds) return vec ? (const void*)k_join_stream<true, false, true, Q2> : (const void*)k_join_stream<true, false, false, Q2>;
+    return vec ? (const void*)k_join_stream<false, false, true, Q2> : (const void*)k_join_stream<false, false, false, Q2>;
+}
+const void* stream_kernel_h3(int pipe, bool lds, bool pairs, bool vec, bool queue2) {
+    return queue2 ? stream_kernel_h3_q<true>(pipe, lds, pairs, vec) : stream_kernel_h3_q<false>(pipe, lds, pairs, vec);
 }
 
 const void* stream_kernel_bng(bool lds, bool pairs, bool vec, bool cpt) {

@@ -1992,7 +1992,7 @@ struct Options {
     int raster_tb_lds = 1;    // tile bases in the stream kernels' LDS: 1 up to 1/3 of it, 2 only when small (1/16), 0 never
     int raster_leaf_lines = 1;  // point raster: line records for single-edge leaf cells (leaf lines; default since round 6)
     int leaf_join = 1;        // k_join_leaf answers the mixed queue's leaf-line rows before k_join_mixed
-    int leaf_blocks_per_cu = 2;  // k_join_leaf grid
+    int leaf_blocks_per_cu = 1;  // k_join_leaf grid (swept 1, 2, 4, 8: profiles/leaf_queue/grid_sweep.txt)
     int exact_defer = 0;      // stream joins: uncertified rows to k_join_h3_exact after k_join_mixed
     int raster_build = 1;     // point raster classification: 1 on the GPU (k_raster_*), 0 on host threads
     int raster_quad_records = 1;  // point raster: LDS quad records beside the quad level
@@ -4553,12 +4553,14 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
             // k_join_stream + k_join_mixed over rows in chunks of < 2^32 (uint32 queue entries)
             const int64_t chunk = ((int64_t)1 << 32) - 256;  // multiple of 256: chunk starts stay aligned
             const int64_t rows = std::min<int64_t>(n, chunk);
-            if ((rc = c->mix_queue.reserve((size_t)rows * 4 + 16))) return rc;
+            // k_join_leaf between the stream and mixed kernels: tables with leaf lines, fixed-point
+            // coordinates (tiles::raster_code_fixed's line offsets).  The stream kernel then queues
+            // two-word entries (stream_kernel_h3 queue2: the row, its tile in 16 bits and its leaf code);
+            // rasters of more tiles send the one-word queue straight to k_join_mixed
+            const bool leafq = c->leaf_join && sa.llines && sa.fix_ok && sa.n_tiles <= 65536;
+            if ((rc = c->mix_queue.reserve((size_t)rows * (leafq ? 8 : 4) + 16))) return rc;
             a.mixq = (uint32_t*)c->mix_queue.p;
             a.mixq_count = sc + 4;
-            // k_join_leaf between the stream and mixed kernels: tables with leaf lines, fixed-point
-            // coordinates (tiles::raster_code_fixed's chain)
-            const bool leafq = c->leaf_join && sa.llines && sa.fix_ok;
             if (leafq && (rc = c->mix_queue2.reserve((size_t)rows * 4 + 16))) return rc;
             // the mixed kernel answers its uncertified rows itself: no exact pass after it (option
             // exact_defer: it queues them for k_join_h3_exact instead)
@@ -4577,7 +4579,7 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
                 if (mode == 1 && !sa.tb_lds) mode = 0;
                 return mode;
             };
-            auto kernel_for = [&](bool vec) -> const void* { return stream_kernel_h3(mode_for(vec), lds, pairs, vec); };
+            auto kernel_for = [&](bool vec) -> const void* { return stream_kernel_h3(mode_for(vec), lds, pairs, vec, leafq); };
             auto shm_for = [&](bool vec) -> size_t {
                 return shm_s + (mode_for(vec) >= 2 ? (size_t)(blk / 64) * kCptBufWords * 4 : 0);
             };
