@@ -116,7 +116,9 @@ int mosaic_destroy(mosaic_ctx* ctx);
  * "raster_build" (1: the point raster is classified on the GPU, the
  * default; 0: on host threads -- identical bytes), "raster_quad" (its LDS level: 0 off, 1 default budget of 32768
  * entries, or an entry budget <= 65536), "stream_block" (k_join_stream workgroup size, a multiple of
- * 64 up to 1024, default 1024), "host_chunk" (rows per chunk when mosaic_pip_join_count gets
+ * 64 up to 1024, default 1024), "stream_grid" (0, the default: the stream kernels' persistent grid;
+ * k in [1, 65536]: at most k workgroups -- a test knob that fixes how many 256-row groups each wave
+ * pipelines; nothing but the two stream launches follows it), "host_chunk" (rows per chunk when mosaic_pip_join_count gets
  * host-resident coordinates: the next chunk's copy overlaps the current chunk's join; 0 = stage the
  * whole batch; default 2^25), "mixed_rows" (1/2/4, default 1), "mixed_blocks_per_cu" (default 16), "cell_blocks_per_cu" (k_cell_h3 grid, default 256; 0 = one lane per row pair), "stream_pipe"
  * (0: k_join_stream; 1: the software-pipelined H3 stream kernel; 2: it with the gathering rows
@@ -166,6 +168,12 @@ int mosaic_last_stats(mosaic_ctx* ctx, int64_t* out3);
 /* Rows the calling thread's last join sorted on its binned path (the points some chip may hold:
  * k_bin_cover's keep count), 0 when the join took another path. */
 int mosaic_last_binned_rows(mosaic_ctx* ctx, int64_t* out);
+/* Queue counts of the calling thread's last join call (of its last chunk of < 2^32 rows): out2[0] rows
+ * the stream kernel queued for the kernels after it (rows its raster could not answer, and rows
+ * outside the raster's range), out2[1] rows k_join_leaf passed on to k_join_mixed (0 without
+ * k_join_leaf: option "leaf_join" = 0, BNG, tables without leaf lines).  Both 0 when the call ran no
+ * stream kernel.  Filled only by sync calls.  For tests that must know a queue path ran. */
+int mosaic_last_queue(mosaic_ctx* ctx, int64_t* out2);
 /* With option "timing" = 1, every join call brackets its fused kernel with HIP events on the
  * context stream.  Waits for the stream, writes up to cap elapsed times (ms) in call order, reports
  * how many calls were timed in *n_out, and resets the list. */

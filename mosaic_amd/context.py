@@ -636,6 +636,13 @@ class MosaicContext:
         N.check(N.lib().mosaic_last_binned_rows(self.handle, N.ptr(out)))
         return int(out[0])
 
+    def last_queue(self):
+        """Queue counts of this thread's last join call: rows its stream kernel queued, and rows
+        k_join_leaf passed on to k_join_mixed; both 0 when no stream kernel ran (mosaic_last_queue)."""
+        out = np.zeros(2, np.int64)
+        N.check(N.lib().mosaic_last_queue(self.handle, N.ptr(out)))
+        return {"stream_queued": int(out[0]), "leaf_forwarded": int(out[1])}
+
     def last_stats(self):
         out = np.zeros(3, np.int64)
         N.check(N.lib().mosaic_last_stats(self.handle, N.ptr(out)))

@@ -2030,6 +2030,11 @@ struct Options {
     // growth by rehashing) and the slot count past which a call returns MOSAIC_E_CAPACITY
     int gk_table_log2 = 16;
     int64_t gk_max_cells = (int64_t)1 << 27;
+    // the stream kernels' grid (both stream launches of run_join): 0, the default, the persistent grid;
+    // k in [1, 65536] caps it at k workgroups, so a test decides how many full 256-row groups (and which
+    // partial one) every wave pipelines.  Nothing else follows it: not the occupancy query, not the
+    // k_join_leaf or k_join_mixed grids
+    int stream_grid = 0;
     // st_distance (st_distance.hip): segments of the staged side per LDS tile of k_dist_block, the
     // facet-pair count up to which a pair goes to k_dist_small, and pruning by box bounds (0: off,
     // for measurements; the result is the same)
@@ -2064,6 +2069,10 @@ struct ThreadCtx : Options {
     binned::Scratch bins;  // the binned join's keys, sorted points and sort temp
     int64_t stats[3] = {0, 0, 0};
     int64_t binned_rows = 0;  // rows the last join's binned path sorted (mosaic_last_binned_rows)
+    // the last join's queue counts, of its last chunk (mosaic_last_queue): [0] rows the stream kernel
+    // queued, [1] rows k_join_leaf passed on to k_join_mixed; both 0 when no stream kernel ran
+    int64_t queue_rows[2] = {0, 0};
+    bool stream_ran = false;  // the last run_join launched a stream kernel
     unsigned int deferred_flags = 0;
     uint64_t last_qcap = 0;  // the exact-H3 queue capacity of the last join (sync_impl's overflow test)
     std::vector<hipEvent_t> ev_start, ev_stop;
@@ -2699,6 +2708,9 @@ int mosaic_set_option(mosaic_ctx* ctx, const char* key, int64_t v) {
     } else if (k == "stream_pipe") {
         if (v < 0 || v > 2) return fail(MOSAIC_E_ARG, "stream_pipe must be 0, 1 or 2");
         o.stream_pipe = (int)v;
+    } else if (k == "stream_grid") {
+        if (v < 0 || v > 65536) return fail(MOSAIC_E_ARG, "stream_grid must be 0 (the persistent grid) or a workgroup count in [1, 65536]");
+        o.stream_grid = (int)v;
     } else if (k == "bng_cpt") {
         o.bng_cpt = v ? 1 : 0;
     } else if (k == "bng_lds") {
@@ -2836,6 +2848,14 @@ int mosaic_last_binned_rows(mosaic_ctx* ctx, int64_t* out) {
     if (!ctx || !out) return fail(MOSAIC_E_ARG, "null argument");
     ENTER(ctx);
     *out = c->binned_rows;
+    return MOSAIC_OK;
+}
+
+int mosaic_last_queue(mosaic_ctx* ctx, int64_t* out2) {
+    if (!ctx || !out2) return fail(MOSAIC_E_ARG, "null argument");
+    ENTER(ctx);
+    out2[0] = c->queue_rows[0];
+    out2[1] = c->queue_rows[1];
     return MOSAIC_OK;
 }
 
@@ -4402,6 +4422,8 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
     }
     unsigned long long* sc = (unsigned long long*)c->scalars.p;
     c->binned_rows = 0;
+    c->queue_rows[0] = c->queue_rows[1] = 0;
+    c->stream_ran = false;
     JoinArgs a;
     a.x = (const double*)dx;
     a.y = (const double*)dy;
@@ -4516,7 +4538,8 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
             auto kernel_for = [&](bool vec) -> const void* {
                 return stream_kernel_bng(lds, pairs, vec, bcpt);
             };
-            c->last_kernel = bcpt ? "k_join_stream_bng_cpt" : "k_join_stream_bng";
+            // (fewer than 256 rows take the non-vector k_join_stream_bng, as below)
+            c->last_kernel = bcpt && std::min<int64_t>(n, chunk) >= 256 ? "k_join_stream_bng_cpt" : "k_join_stream_bng";
             int per_cu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_for(true), blkb, shm_b) != hipSuccess || per_cu < 1)
                 per_cu = 1;
@@ -4526,8 +4549,10 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
                 ac.n = std::min<int64_t>(n, lo + chunk);
                 if (lo > 0) HIP_TRY(hipMemsetAsync(ac.mixq_count, 0, 8, c->stream));
                 const void* kfn = kernel_for(aligned && ac.n - lo >= 256);
-                const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((ac.n - lo + 4 * blkb - 1) / (4 * blkb),
-                                                                           (int64_t)c->n_cu * per_cu));
+                int gs = (int)std::max<int64_t>(1, std::min<int64_t>((ac.n - lo + 4 * blkb - 1) / (4 * blkb),
+                                                                     (int64_t)c->n_cu * per_cu));
+                if (c->stream_grid > 0) gs = std::min(gs, c->stream_grid);  // option stream_grid (a test knob)
+                c->stream_ran = true;
                 void* kargs[] = {&ac, &bs};
                 HIP_TRY(hipLaunchKernel(kfn, dim3(gs), dim3(blkb), kargs, shm_b, c->stream));
                 if (tstop && lo == 0) HIP_TRY(hipEventRecord(tstop, c->stream));
@@ -4601,8 +4626,10 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
                 }
                 if (lo > 0) HIP_TRY(hipMemsetAsync(ac.mixq_count, 0, 8, c->stream));
                 // persistent grid: the workgroups resident at once (each fills its LDS once)
-                const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((ac.n - lo + 4 * blk - 1) / (4 * blk),
-                                                                           (int64_t)c->n_cu * per_cu));
+                int gs = (int)std::max<int64_t>(1, std::min<int64_t>((ac.n - lo + 4 * blk - 1) / (4 * blk),
+                                                                     (int64_t)c->n_cu * per_cu));
+                if (c->stream_grid > 0) gs = std::min(gs, c->stream_grid);  // option stream_grid (a test knob)
+                c->stream_ran = true;
                 void* kargs[] = {&ac, &sa};
                 HIP_TRY(hipLaunchKernel(kfn, dim3(gs), dim3(blk), kargs, shm_for(aligned && ac.n - lo >= 256), c->stream));
                 if (tstop && lo == 0) HIP_TRY(hipEventRecord(tstop, c->stream));
@@ -4725,6 +4752,10 @@ static int run_join(ThreadCtx* c, const mosaic_chips* ch, const double* x, const
     c->stats[0] = (int64_t)s[0];
     c->stats[1] = (int64_t)s[2];
     c->stats[2] = (int64_t)s[1];
+    if (c->stream_ran) {
+        c->queue_rows[0] = (int64_t)s[4];
+        c->queue_rows[1] = (int64_t)s[7];
+    }
     if (s[3] & 1u) return fail(MOSAIC_E_NAN, "NaN coordinates are not supported.");
     if (counts && !dev_counts) HIP_TRY(hipMemcpy(counts, dcounts, (size_t)ch->n_polygons * 8, hipMemcpyDeviceToHost));
     if (pairs) {
@@ -4788,6 +4819,10 @@ static int join_count_host_chunked(ThreadCtx* c, const mosaic_chips* ch, const d
             HIP_TRY(hipMemcpy(s, c->scalars.p, sizeof s, hipMemcpyDeviceToHost));
             c->stats[0] = (int64_t)s[0];
             c->stats[1] = (int64_t)s[2];
+            if (c->stream_ran) {
+                c->queue_rows[0] = (int64_t)s[4];
+                c->queue_rows[1] = (int64_t)s[7];
+            }
         }
         st0 += c->stats[0];
         st1 += c->stats[1];
