@@ -809,6 +809,36 @@ int mosaic_neighbours_destroy(mosaic_neighbours* nb);
  * mosaic_ring_neighbours, ms; split3 (nullable): probe + de-duplication + self-match filter, distance, order. */
 double mosaic_ring_neighbours_last_ms(double* split3);
 
+/* ---- the distance-within join: all (landmark, candidate) pairs with st_distance <= radius ---- */
+/* Row i asks for landmark left_row[i] with radius[i]; left_row == NULL: rows 0 .. n - 1 of `left`,
+ * otherwise strictly ascending rows of `left`.  (l, c) is a pair iff both rows are MOSAIC_ROW_OK, both
+ * have at least one facet, radius >= 0 and the bits of mosaic_st_distance(left[l], right[c]) are <=
+ * the radius' bits.  An empty geometry is within distance of nothing (mosaic_st_distance's 0.0 for
+ * it does not count, as in mosaic_st_intersects); null and row-path rows never pair.  A NaN or
+ * negative radius gives its row no pairs; +inf and DBL_MAX accept every eligible candidate; -0.0 is 0.
+ * Self matches (as in mosaic_ring_neighbours) are dropped unless keep_self.  The result is a
+ * mosaic_neighbours ordered by (l, distance bits, c) whose unmatched[] is all zero:
+ * mosaic_neighbours_info / _export / _destroy serve it.  The rows are those of the sequential
+ * definition rn::within in mosaic_amd/csrc/ring_neighbours.h, which looks at all pairs.
+ * The candidates are found by an envelope filter over all (requested row, candidate row) pairs
+ * (k_wn_count / k_wn_emit) that can drop no pair; mosaic_within_candidates returns that filter's own
+ * count per requested row -- the eligible candidates c with dist::box_lower_bound(box(l), box(c)) <=
+ * radius[i], rn::within_candidates -- so that a caller can size its calls.  left_row / radius /
+ * counts: host or device pointers.  Options: "within_tile" (candidate boxes per LDS tile, [1, 1024],
+ * default 256) and "within_slices" (slices of the candidate rows, a second grid dimension; 0 =
+ * enough to fill the device); neither changes a row.
+ * Errors, with nothing written: MOSAIC_E_ARG for a null context (before any device work), for a row
+ * outside `left` or rows that are not strictly ascending, for columns of another device, or 2^31 or
+ * more rows; MOSAIC_E_CAPACITY for 2^31 or more candidate pairs in one call. */
+int mosaic_within_candidates(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right,
+                             const int64_t* left_row /*nullable*/, const double* radius, int64_t n, int64_t* counts);
+int mosaic_within_neighbours(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right,
+                             const int64_t* left_row /*nullable*/, const double* radius, int64_t n, int keep_self,
+                             mosaic_neighbours** out);
+/* Device time of the calling thread's last mosaic_within_neighbours, ms; split3 (nullable): filter +
+ * self-match filter, distance + radius select, order. */
+double mosaic_within_neighbours_last_ms(double* split3);
+
 /* getBufferRadius(geometry, res) per geometry (the radius mosaicFill buffers by, core/Mosaic.scala:68):
  * H3 (H3IndexSystem.scala:73-80): the largest distance (degrees) from the centroid of the cell
  * holding the geometry's JTS centroid (its indexToGeometry polygon's JTS centroid) to that polygon's

@@ -56,6 +56,7 @@ EXPORTS = [
     "mosaic_line_intersection_last", "mosaic_line_intersection_aggregate_host",
     "mosaic_st_intersects", "mosaic_st_intersects_last_split",
     "mosaic_st_measures", "mosaic_st_measures_last_split",
+    "mosaic_within_candidates", "mosaic_within_neighbours", "mosaic_within_neighbours_last_ms",
 ]
 
 GEOM_WKB = 0
@@ -203,6 +204,9 @@ def lib():
         "mosaic_neighbours_export": ([vp, vp, vp, vp, vp], i32),
         "mosaic_neighbours_destroy": ([vp], i32),
         "mosaic_ring_neighbours_last_ms": ([vp], ctypes.c_double),
+        "mosaic_within_candidates": ([vp, vp, vp, vp, vp, i64, vp], i32),
+        "mosaic_within_neighbours": ([vp, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)], i32),
+        "mosaic_within_neighbours_last_ms": ([vp], ctypes.c_double),
         "mosaic_buffer_radius": ([vp, i32, i32, i64, vp, vp, vp, vp, vp], i32),
         "mosaic_chip_table_create_arrays": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)], i32),
         "mosaic_intersection_aggregate": ([vp, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64)], i32),

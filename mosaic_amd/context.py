@@ -1106,6 +1106,24 @@ class MosaicContext:
 
         return grid_ring_neighbours(self, landmarks, candidates, cell_index, rows, cells, keep_self)
 
+    def st_dwithin_join(self, left, right, radius, rows=None, keep_self=True):
+        """The distance-within join: ``(left_row, right_row, distance)`` of all pairs with
+        ``st_distance(left[l], right[c]) <= radius`` -- one radius for all rows or one per requested row,
+        ``rows`` the left rows asked for (strictly ascending; None: all) -- ordered by (left row,
+        distance, right row).  With radius 0 it is the pair list of the geometries that touch or
+        overlap.  See ``knn.within_neighbours``."""
+        from .knn import within_neighbours
+
+        return within_neighbours(self, left, right, radius, rows, keep_self)
+
+    def st_dwithin_candidates(self, left, right, radius, rows=None):
+        """Per requested row, the number of candidate pairs ``st_dwithin_join``'s envelope filter finds
+        (int64, at least the row's pairs): what a caller sizes its calls by.  See
+        ``knn.within_candidates``."""
+        from .knn import within_candidates
+
+        return within_candidates(self, left, right, radius, rows)
+
     # ---- the chip join ----
     def grid_tessellateexplode(self, polygons, resolution, keep_core_geom=True, densify=1, cells_only=False):
         """grid_tessellateexplode(geom, res, keepCoreGeom) (MosaicContext.scala functions ->

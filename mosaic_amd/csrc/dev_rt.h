@@ -17,6 +17,7 @@
 extern "C" int mosaic_ctx_gk_options(mosaic_ctx* ctx, int* table_log2, int64_t* max_cells);          // geom_kring.hip
 extern "C" int mosaic_ctx_dist_options(mosaic_ctx* ctx, int* tile, int64_t* small_work, int* prune);  // the pair kernels
 extern "C" int mosaic_ctx_meas_options(mosaic_ctx* ctx, int* tile, int64_t* wave_min);                // st_measures.hip
+extern "C" int mosaic_ctx_within_options(mosaic_ctx* ctx, int* tile, int* slices);                    // the distance-within join
 
 // the one HIP error macro: out of memory is MOSAIC_E_NOMEM, everything else MOSAIC_E_HIP
 #define MOSAIC_HIP(expr)                                                         \

@@ -2045,6 +2045,10 @@ struct Options {
     // from which a row takes a wave instead of one lane
     int meas_tile = 256;
     int64_t meas_wave_min = 128;
+    // the distance-within join (ring_neighbours.hip): candidate boxes per LDS tile of k_wn_count /
+    // k_wn_emit, and the slices the candidate rows are cut into (0: enough to fill the device)
+    int within_tile = 256;
+    int within_slices = 0;
 };
 
 // Execution state of one calling thread on one context: its HIP stream (created on first use, or
@@ -2436,6 +2440,15 @@ int mosaic_ctx_meas_options(mosaic_ctx* ctx, int* tile, int64_t* wave_min) {
     return MOSAIC_OK;
 }
 
+// the "within_tile" / "within_slices" options, for ring_neighbours.hip
+int mosaic_ctx_within_options(mosaic_ctx* ctx, int* tile, int* slices) {
+    if (!ctx) return fail(MOSAIC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *tile = ctx->opt.within_tile;
+    *slices = ctx->opt.within_slices;
+    return MOSAIC_OK;
+}
+
 // what k_isect_agg reads from a chip table, for line_join.hip
 int mosaic_chips_join_view(const mosaic_chips* chips, ChipsJoinView* out) {
     if (!chips || !out) return fail(MOSAIC_E_ARG, "null chip table");
@@ -2764,6 +2777,12 @@ int mosaic_set_option(mosaic_ctx* ctx, const char* key, int64_t v) {
     } else if (k == "meas_wave_min") {
         if (v < 0) return fail(MOSAIC_E_ARG, "meas_wave_min must be >= 0");
         o.meas_wave_min = v;
+    } else if (k == "within_tile") {
+        if (v < 1 || v > 1024) return fail(MOSAIC_E_ARG, "within_tile must be in [1, 1024]");
+        o.within_tile = (int)v;
+    } else if (k == "within_slices") {
+        if (v < 0 || v > 65535) return fail(MOSAIC_E_ARG, "within_slices must be in [0, 65535]");
+        o.within_slices = (int)v;
     } else {
         return fail(MOSAIC_E_ARG, "unknown option " + k);
     }

@@ -210,6 +210,95 @@ inline int neighbours(const CellIndexView& ix, const Col& L, const Col& C, const
     return 0;
 }
 
+// ---- the distance-within join ----
+// All (landmark, candidate) pairs with st_distance <= radius[landmark]: the candidates come from the
+// geometries themselves, not from a cell index.  Row i asks for landmark left_row[i] (null: row i)
+// with radius[i]; left_row is strictly ascending, so a landmark is asked for once.
+//   * (l, c) is a pair iff both rows are eligible -- MOSAIC_ROW_OK with at least one facet -- and
+//     within_radius(dist::distance(l, c), radius).  An empty geometry is within distance of nothing
+//     (dist::distance's 0.0 for it does not leak, st_intersects' stance); null and row-path rows
+//     never pair, so no distance here is NaN.
+//   * A NaN or negative radius gives its row no pairs; +inf and DBL_MAX accept every eligible
+//     candidate; -0.0 is the radius 0.
+//   * Self matches are dropped unless keep_self (self_match, as above).
+//   * Order: (landmark row, distance bits, candidate row); unmatched[] is all zero.
+// `within` below is the definition of the result: plain loops over all pairs, no filter of any kind.
+//
+// The kernels find their candidates with an envelope filter, and within_candidates is that filter's
+// own count: the eligible candidates c with dist::box_lower_bound(bbox(l), bbox(c)) <= radius[i].
+// The filter drops no pair: for eligible rows with finite coordinates box_lower_bound is at most
+// the bits dist::distance computes (st_distance.h; both geometries have a facet, every facet lies
+// in its geometry's box, and a contained component gives 0.0 over meeting boxes, whose bound is
+// <= 0), so distance <= radius implies bound <= radius, also for radius = +inf.  Eligibility is
+// decided from the status and the facet count, never from the box: the empty box
+// {inf, inf, -inf, -inf} has the bound +inf against a finite box, which the radius +inf accepts.
+MOSAIC_HD bool eligible(const Col& c, int64_t g) { return c.status[g] == 1 && c.facets[g] > 0; }  // 1: MOSAIC_ROW_OK
+
+MOSAIC_HD bool radius_ok(double r) { return r >= 0; }  // false for NaN
+
+// d is a number >= 0 here, so the order of the bits is the order of the values
+MOSAIC_HD bool within_radius(double d, double r) { return radius_ok(r) && bits_of(d) <= bits_of(r + 0.0); }
+
+MOSAIC_HD bool box_within(const pip::Box& a, const pip::Box& b, double r) { return dist::box_lower_bound(a, b) <= r; }
+
+// 0, or 1 when the rows are not strictly ascending rows of L (left_row null: n > L.n)
+inline int within_rows_check(const Col& L, const int64_t* left_row, int64_t n) {
+    if (n < 0 || (!left_row && n > L.n)) return 1;
+    if (left_row)
+        for (int64_t i = 0; i < n; i++)
+            if (left_row[i] < 0 || left_row[i] >= L.n || (i > 0 && left_row[i - 1] >= left_row[i])) return 1;
+    return 0;
+}
+
+// counts[i]: the filter's candidates of row i.  1 with nothing written on a row error.
+inline int within_candidates(const Col& L, const Col& C, const int64_t* left_row, const double* radius, int64_t n, int64_t* counts) {
+    if (within_rows_check(L, left_row, n)) return 1;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t l = left_row ? left_row[i] : i;
+        int64_t k = 0;
+        if (eligible(L, l) && radius_ok(radius[i]))
+            for (int64_t c = 0; c < C.n; c++)
+                if (eligible(C, c) && box_within(L.s.geom_bbox[l], C.s.geom_bbox[c], radius[i])) k++;
+        counts[i] = k;
+    }
+    return 0;
+}
+
+// 1 with nothing written on a row error
+inline int within(const Col& L, const Col& C, const int64_t* left_row, const double* radius, int64_t n, bool keep_self,
+                  Neighbours* out) {
+    if (within_rows_check(L, left_row, n)) return 1;
+    *out = Neighbours();
+    out->unmatched.assign((size_t)L.n, 0);
+    struct Row {
+        uint64_t l, d, c;
+    };
+    std::vector<Row> rows;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t l = left_row ? left_row[i] : i;
+        if (!eligible(L, l) || !radius_ok(radius[i])) continue;
+        for (int64_t c = 0; c < C.n; c++) {
+            if (!eligible(C, c)) continue;
+            if (!keep_self && self_match(L, (uint32_t)l, C, (uint32_t)c)) continue;
+            const double d = dist::distance(L.s, L.part_kind, (uint32_t)l, C.s, C.part_kind, (uint32_t)c);
+            if (within_radius(d, radius[i])) rows.push_back(Row{(uint64_t)l, bits_of(d), (uint64_t)c});
+        }
+    }
+    std::sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
+        if (a.l != b.l) return a.l < b.l;
+        if (a.d != b.d) return a.d < b.d;
+        return a.c < b.c;
+    });
+    for (const Row& r : rows) {
+        out->left_row.push_back((int64_t)r.l);
+        out->right_row.push_back((int64_t)r.c);
+        double d;
+        __builtin_memcpy(&d, &r.d, sizeof d);
+        out->distance.push_back(d);
+    }
+    return 0;
+}
+
 // layout fingerprint of what ring_neighbours.hip shares with the other translation units (join_binned.h's rationale)
 static constexpr uint64_t layout_fingerprint() {
     uint64_t h = 0xcbf29ce484222325ULL;

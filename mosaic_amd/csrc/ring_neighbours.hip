@@ -25,6 +25,16 @@
 //
 // The reference's st_intersects_aggregate filter is a no-op in this join (ring_neighbours.h) and is
 // not built.
+//
+// The distance-within join (mosaic_within_candidates, mosaic_within_neighbours) finds its pairs without
+// a cell index and then runs the same tail (finish_pairs):
+//   k_wn_count   the envelope filter of every requested landmark against every candidate row, dense:
+//                256 landmarks per workgroup in registers, the candidates' boxes through LDS, one
+//                count per (row, candidate slice)
+//   device scan  of the counts
+//   k_wn_emit    the same walk again, writing the keys at the scanned places: distinct and ascending
+//   k_rn_self, mosaic_st_distance as above, then k_wn_keep + two flagged selects keep the pairs whose
+//   distance bits are within their row's radius, then the order as above
 #include <memory>
 
 #include "dev_rt.h"
@@ -206,7 +216,275 @@ __global__ void __launch_bounds__(kBlock) k_rn_narrow(const uint32_t* in, int64_
         out[i] = in[i] ? 1 : 0;
 }
 
+// ---- the distance-within join: the envelope filter ----
+// A workgroup takes kBlock requested rows, one per lane: the landmark's box and radius stay in
+// registers.  blockIdx.y is a slice of the candidate rows, [y * slice_len, (y + 1) * slice_len): its
+// boxes pass through LDS `tile` at a time, with the eligibility (status and facet count) decided as a
+// box is staged, and every lane walks the tile at the same address (a broadcast read).  The decision
+// is rn::box_within alone.  k_wn_count writes one count per (row, slice), row-major; their exclusive
+// sum gives k_wn_emit, which repeats the walk, the place of every key: the keys come out distinct and
+// ascending by (landmark, candidate) with no sort and no atomic.
+struct WithinArgs {
+    const pip::Box *lbox, *cbox;
+    const int32_t *lstatus, *cstatus;
+    const uint32_t *lfacets, *cfacets;
+    const int64_t* left_row;  // null: row i asks for landmark i
+    const double* radius;
+    int64_t n, n_left, n_cand, slice_len;  // slice_len: a multiple of tile
+    int tile, slices;
+    uint64_t* cnt;            // [n * slices]
+    const uint64_t* off;      // emit: [n * slices + 1], the exclusive sum of cnt and the total
+    uint64_t* keys;           // emit
+    unsigned long long* bad;  // count: rows outside the landmark column or not strictly ascending
+};
+
+template <bool kEmit>
+__device__ __forceinline__ void wn_walk(const WithinArgs& a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wn_lds[];
+    pip::Box* s_box = (pip::Box*)wn_lds;
+    uint8_t* s_ok = (uint8_t*)(s_box + a.tile);
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t s = blockIdx.y;
+    bool live = false;
+    pip::Box lb{0, 0, 0, 0};
+    double r = -1;
+    int64_t l = -1;
+    if (i < a.n) {
+        l = a.left_row ? a.left_row[i] : i;
+        const bool in = l >= 0 && l < a.n_left && (!a.left_row || i == 0 || a.left_row[i - 1] < l);
+        if (!in) {
+            if (!kEmit && s == 0) atomicAdd(a.bad, 1ull);
+        } else {
+            r = a.radius[i];
+            live = a.lstatus[l] == 1 && a.lfacets[l] > 0 && rn::radius_ok(r);
+            if (live) lb = a.lbox[l];
+        }
+    }
+    const int64_t slot = i * a.slices + s;
+    uint64_t pos = 0, end = 0;
+    if (kEmit && i < a.n) {
+        pos = a.off[slot];
+        end = a.off[slot + 1];
+    }
+    const int64_t c0 = s * a.slice_len, c1 = c0 + a.slice_len < a.n_cand ? c0 + a.slice_len : a.n_cand;
+    for (int64_t t0 = c0; t0 < c1; t0 += a.tile) {
+        const int m = (int)(c1 - t0 < a.tile ? c1 - t0 : a.tile);
+        __syncthreads();  // the last tile has been walked
+        for (int j = threadIdx.x; j < m; j += kBlock) {
+            const int64_t c = t0 + j;
+            s_box[j] = a.cbox[c];
+            s_ok[j] = a.cstatus[c] == 1 && a.cfacets[c] > 0;
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int j = 0; j < m; j++) {
+            if (!s_ok[j]) continue;  // uniform
+            if (rn::box_within(lb, s_box[j], r)) {
+                if (kEmit && pos < end) a.keys[pos] = rn::pack_pair(l, t0 + j);
+                pos++;
+            }
+        }
+    }
+    if (!kEmit && i < a.n) a.cnt[slot] = pos;
+}
+
+__global__ void __launch_bounds__(kBlock) k_wn_count(WithinArgs a) { wn_walk<false>(a); }
+__global__ void __launch_bounds__(kBlock) k_wn_emit(WithinArgs a) { wn_walk<true>(a); }
+
+// the filter's count of a row: the sum over its slices
+__global__ void __launch_bounds__(kBlock) k_wn_rowsum(const uint64_t* cnt, int64_t n, int slices, int64_t* out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t t = 0;
+        for (int s = 0; s < slices; s++) t += cnt[i * slices + s];
+        out[i] = (int64_t)t;
+    }
+}
+
+// keep[p] = the pair's distance is within the radius its landmark's row asked for (left_row ascending: a binary search)
+__global__ void __launch_bounds__(kBlock) k_wn_keep(const uint64_t* keys, const double* distance, int64_t n_pairs, const int64_t* left_row,
+                                                    const double* radius, int64_t n, uint8_t* keep) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_pairs; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = (int64_t)(keys[p] >> 32);
+        int64_t i = l;
+        if (left_row) {
+            int64_t lo = 0, hi = n - 1;  // l is one of the rows
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if (left_row[mid] < l)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            i = lo;
+        }
+        keep[p] = rn::within_radius(distance[p], radius[i]) ? 1 : 0;
+    }
+}
+
 thread_local double g_last_ms[3] = {0, 0, 0};
+thread_local double g_within_ms[3] = {0, 0, 0};
+
+template <class T>
+int select_flagged(Buf& tmp, const T* in, const uint8_t* flags, T* out, int64_t* d_num, int64_t n, hipStream_t st) {
+    size_t bytes = 0;
+    MOSAIC_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, in, flags, out, d_num, (int)n, st));
+    MOSAIC_RC(tmp.reserve(bytes));
+    bytes = tmp.bytes;
+    MOSAIC_HIP(hipcub::DeviceSelect::Flagged(tmp.p, bytes, in, flags, out, d_num, (int)n, st));
+    return MOSAIC_OK;
+}
+
+// what the radius select of the distance-within join reads: the requested rows and their radii, on the device
+struct RadiusSelect {
+    const int64_t* left_row;  // nullable
+    const double* radius;
+    int64_t n;
+};
+
+// The tail both joins share.  k0 holds n_pairs distinct (landmark, candidate) keys, ascending; k1 has
+// room for as many.  Self matches are dropped unless keep_self, mosaic_st_distance measures the pairs,
+// `sel` (the distance-within join only) keeps the pairs within their row's radius, and two stable
+// sorts order the rows by (landmark, distance bits, candidate) into nb's own arrays.  ev[1] .. ev[3]
+// are recorded after the self filter, after the distances (and the select) and at the end.
+int finish_pairs(mosaic_ctx* ctx, const dev::Exec& ex, const mosaic_geoms* left, const mosaic_geoms* right, Buf& k0, Buf& k1,
+                 int64_t n_pairs, int keep_self, const RadiusSelect* sel, mosaic_neighbours* nb, dev::Events<4>& ev) {
+    hipStream_t st = ex.stream;
+    const int64_t wide = (int64_t)ex.n_cu * 16;
+    const int64_t n_left = left->n_geoms;
+    Buf d_num, d_keep, d_tmp, d_l, d_r, d_d0, d_d1, d_p1;
+    MOSAIC_RC(d_num.reserve(8));
+    uint64_t* pairs = k0.as<uint64_t>();
+    uint64_t* other = k1.as<uint64_t>();
+    if (!keep_self && n_pairs > 0) {
+        MOSAIC_RC(d_keep.reserve((size_t)n_pairs));
+        hipLaunchKernelGGL(k_rn_self, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, view(left), view(right), pairs, n_pairs,
+                           d_keep.as<uint8_t>());
+        MOSAIC_HIP(hipGetLastError());
+        MOSAIC_RC(select_flagged(d_tmp, pairs, d_keep.as<uint8_t>(), other, d_num.as<int64_t>(), n_pairs, st));
+        MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
+        std::swap(pairs, other);
+    }
+    const uint64_t* dist_bits = nullptr;  // the kept pairs' distances
+    if (!sel) {
+        nb->n_pairs = n_pairs;
+        const size_t pb = std::max<size_t>((size_t)n_pairs * 8, 16);
+        MOSAIC_HIP(hipMalloc((void**)&nb->left_row, pb));
+        MOSAIC_HIP(hipMalloc((void**)&nb->right_row, pb));
+        MOSAIC_HIP(hipMalloc((void**)&nb->distance, pb));
+        if (n_pairs > 0) {
+            hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, pairs, n_pairs, nb->left_row,
+                               nb->right_row);
+            MOSAIC_HIP(hipGetLastError());
+        }
+        MOSAIC_HIP(hipEventRecord(ev.e[1], st));
+        if (n_pairs > 0) MOSAIC_RC(mosaic_st_distance(ctx, left, right, nb->left_row, nb->right_row, n_pairs, nb->distance, nullptr));
+        dist_bits = (const uint64_t*)nb->distance;
+    } else {
+        // the candidates may be many more than the pairs within: they are measured in scratch, and the
+        // result's arrays get the size the select leaves
+        if (n_pairs > 0) {
+            MOSAIC_RC(d_l.reserve((size_t)n_pairs * 8));
+            MOSAIC_RC(d_r.reserve((size_t)n_pairs * 8));
+            MOSAIC_RC(d_d0.reserve((size_t)n_pairs * 8));
+            hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, pairs, n_pairs, d_l.as<int64_t>(),
+                               d_r.as<int64_t>());
+            MOSAIC_HIP(hipGetLastError());
+        }
+        MOSAIC_HIP(hipEventRecord(ev.e[1], st));
+        if (n_pairs > 0) {
+            MOSAIC_RC(mosaic_st_distance(ctx, left, right, d_l.as<int64_t>(), d_r.as<int64_t>(), n_pairs, d_d0.as<double>(), nullptr));
+            MOSAIC_RC(d_keep.reserve((size_t)n_pairs));
+            hipLaunchKernelGGL(k_wn_keep, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, pairs, d_d0.as<double>(), n_pairs,
+                               sel->left_row, sel->radius, sel->n, d_keep.as<uint8_t>());
+            MOSAIC_HIP(hipGetLastError());
+            // d_l is free again: the kept distances go there
+            MOSAIC_RC(select_flagged(d_tmp, pairs, d_keep.as<uint8_t>(), other, d_num.as<int64_t>(), n_pairs, st));
+            MOSAIC_RC(select_flagged(d_tmp, d_d0.as<uint64_t>(), d_keep.as<uint8_t>(), d_l.as<uint64_t>(), d_num.as<int64_t>(), n_pairs, st));
+            MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
+            MOSAIC_HIP(hipStreamSynchronize(st));
+            std::swap(pairs, other);
+            dist_bits = d_l.as<uint64_t>();
+        }
+        nb->n_pairs = n_pairs;
+        const size_t pb = std::max<size_t>((size_t)n_pairs * 8, 16);
+        MOSAIC_HIP(hipMalloc((void**)&nb->left_row, pb));
+        MOSAIC_HIP(hipMalloc((void**)&nb->right_row, pb));
+        MOSAIC_HIP(hipMalloc((void**)&nb->distance, pb));
+    }
+    MOSAIC_HIP(hipEventRecord(ev.e[2], st));
+    if (n_pairs > 0) {
+        // `pairs` is ordered by (landmark, candidate): stable by distance bits, then stable by landmark (the
+        // second sort leaves the distances in the result's own array)
+        MOSAIC_RC(d_d1.reserve((size_t)n_pairs * 8));
+        MOSAIC_RC(d_p1.reserve((size_t)n_pairs * 8));
+        MOSAIC_RC(dev::sort_pairs(d_tmp, dist_bits, d_d1.as<uint64_t>(), pairs, d_p1.as<uint64_t>(), (int)n_pairs, 0, 64, st));
+        MOSAIC_RC(dev::sort_pairs(d_tmp, d_p1.as<uint64_t>(), other, d_d1.as<uint64_t>(), (uint64_t*)nb->distance, (int)n_pairs, 32, 32 + bits_for(n_left), st));
+        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, other, n_pairs, nb->left_row,
+                           nb->right_row);
+        MOSAIC_HIP(hipGetLastError());
+    }
+    MOSAIC_HIP(hipEventRecord(ev.e[3], st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
+    return MOSAIC_OK;
+}
+
+// The count pass of the distance-within join, shared by its two entries: the rows and radii on the
+// device, the grid, and k_wn_count's counts in p.cnt.  MOSAIC_E_ARG when a row is outside the landmark
+// column or the rows are not strictly ascending.
+struct WithinPlan {
+    Buf s_lrow, s_rad, cnt, bad;
+    WithinArgs a;
+    dim3 grid;
+    size_t lds = 0;
+};
+
+int within_count(mosaic_ctx* ctx, const dev::Exec& ex, const char* who, const mosaic_geoms* left, const mosaic_geoms* right,
+                 const int64_t* left_row, const double* radius, int64_t n, WithinPlan& p) {
+    hipStream_t st = ex.stream;
+    int tile = 256, slices_opt = 0;
+    MOSAIC_RC(mosaic_ctx_within_options(ctx, &tile, &slices_opt));
+    const int64_t n_cand = right->n_geoms;
+    const int64_t blocks_x = (n + kBlock - 1) / kBlock;
+    const int64_t n_tiles = std::max<int64_t>(1, (n_cand + tile - 1) / tile);
+    // automatic: enough slices that four workgroups per CU have work, each at least one tile long
+    int64_t slices = slices_opt > 0 ? slices_opt : ((int64_t)ex.n_cu * 4 + blocks_x - 1) / blocks_x;
+    slices = std::max<int64_t>(1, std::min<int64_t>({slices, n_tiles, 65535, (rn::kMaxRows - 1) / std::max<int64_t>(n, 1)}));
+    const int64_t slice_len = ((n_tiles + slices - 1) / slices) * tile;
+    slices = std::max<int64_t>(1, (n_cand + slice_len - 1) / slice_len);
+    p.a = WithinArgs{left->geom_bbox, right->geom_bbox, left->row_status, right->row_status, left->geom_facets, right->geom_facets,
+                     nullptr, nullptr, n, left->n_geoms, n_cand, slice_len, tile, (int)slices, nullptr, nullptr, nullptr, nullptr};
+    if (left_row) MOSAIC_RC(dev::on_device(left_row, n, p.s_lrow, st, &p.a.left_row));
+    MOSAIC_RC(dev::on_device(radius, n, p.s_rad, st, &p.a.radius));
+    MOSAIC_RC(p.cnt.reserve((size_t)(n * slices) * 8));
+    MOSAIC_RC(p.bad.reserve(8));
+    MOSAIC_HIP(hipMemsetAsync(p.bad.p, 0, 8, st));
+    p.a.cnt = p.cnt.as<uint64_t>();
+    p.a.bad = p.bad.as<unsigned long long>();
+    p.grid = dim3((unsigned)blocks_x, (unsigned)slices);
+    p.lds = ((size_t)tile * (sizeof(pip::Box) + 1) + 15) & ~(size_t)15;
+    hipLaunchKernelGGL(k_wn_count, p.grid, dim3(kBlock), p.lds, st, p.a);
+    MOSAIC_HIP(hipGetLastError());
+    unsigned long long bad = 0;
+    MOSAIC_HIP(hipMemcpyAsync(&bad, p.bad.p, 8, hipMemcpyDeviceToHost, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
+    if (bad)
+        return mosaic_tess_fail(MOSAIC_E_ARG, (std::string(who) + ": " + std::to_string(bad) +
+                                               " row(s) outside the landmark column or not strictly ascending").c_str());
+    return MOSAIC_OK;
+}
+
+// the checks both entries make before any device work
+int within_args(const char* who, mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                const double* radius, int64_t n, bool has_out) {
+    if (!ctx) return mosaic_tess_fail(MOSAIC_E_ARG, (std::string(who) + ": null context").c_str());
+    if (!left || !right || !has_out || n < 0 || (n > 0 && !radius)) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    if (n >= rn::kMaxRows || left->n_geoms >= rn::kMaxRows || right->n_geoms >= rn::kMaxRows)
+        return mosaic_tess_fail(MOSAIC_E_ARG, (std::string(who) + ": 2^31 - 1 rows at the most").c_str());
+    if (!left_row && n > left->n_geoms)
+        return mosaic_tess_fail(MOSAIC_E_ARG, (std::string(who) + ": more rows than the landmark column holds").c_str());
+    return MOSAIC_OK;
+}
 
 }  // namespace
 
@@ -324,7 +602,7 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
     MOSAIC_RC(ev.create());
     MOSAIC_HIP(hipEventRecord(ev.e[0], st));
 
-    Buf s_lrow, s_cell, d_un, d_slot, d_cnt, d_off, d_bad, d_tmp, d_k0, d_k1, d_num, d_keep;
+    Buf s_lrow, s_cell, d_un, d_slot, d_cnt, d_off, d_bad, d_tmp, d_k0, d_k1, d_num;
     MOSAIC_RC(d_un.reserve((size_t)n_left * 4));
     MOSAIC_HIP(hipMemsetAsync(d_un.p, 0, std::max<size_t>((size_t)n_left * 4, 16), st));
     MOSAIC_HIP(hipMalloc((void**)&nb->unmatched, std::max<size_t>((size_t)n_left, 16)));
@@ -363,8 +641,7 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
     hipLaunchKernelGGL(k_rn_narrow, dim3(blocks_for(n_left, kBlock, wide)), dim3(kBlock), 0, st, d_un.as<uint32_t>(), n_left, nb->unmatched);
     MOSAIC_HIP(hipGetLastError());
 
-    int64_t n_pairs = 0;
-    uint64_t* pairs = nullptr;  // (landmark, candidate) keys, distinct and ascending
+    int64_t n_pairs = 0;  // (landmark, candidate) keys in d_k0, distinct and ascending
     if (total > 0) {
         MOSAIC_RC(d_k0.reserve((size_t)total * 8));
         MOSAIC_RC(d_k1.reserve((size_t)total * 8));
@@ -374,7 +651,7 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
         size_t bytes = 0;
         const int end_bit = 32 + bits_for(n_left);
         MOSAIC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
-        Buf t1, t2, t3;
+        Buf t1, t2;
         MOSAIC_RC(t1.reserve(bytes));
         MOSAIC_HIP(hipcub::DeviceRadixSort::SortKeys(t1.p, bytes, d_k0.as<uint64_t>(), d_k1.as<uint64_t>(), (int)total, 0, end_bit, st));
         bytes = 0;
@@ -383,51 +660,8 @@ int mosaic_ring_neighbours(mosaic_ctx* ctx, const mosaic_cell_index* index, cons
         MOSAIC_HIP(hipcub::DeviceSelect::Unique(t2.p, bytes, d_k1.as<uint64_t>(), d_k0.as<uint64_t>(), d_num.as<int64_t>(), (int)total, st));
         MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
         MOSAIC_HIP(hipStreamSynchronize(st));
-        pairs = d_k0.as<uint64_t>();
-        if (!keep_self && n_pairs > 0) {
-            MOSAIC_RC(d_keep.reserve((size_t)n_pairs));
-            hipLaunchKernelGGL(k_rn_self, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, view(left), view(right), pairs, n_pairs,
-                               d_keep.as<uint8_t>());
-            MOSAIC_HIP(hipGetLastError());
-            bytes = 0;
-            MOSAIC_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
-                                                 (int)n_pairs, st));
-            MOSAIC_RC(t3.reserve(bytes));
-            MOSAIC_HIP(hipcub::DeviceSelect::Flagged(t3.p, bytes, pairs, d_keep.as<uint8_t>(), d_k1.as<uint64_t>(), d_num.as<int64_t>(),
-                                                 (int)n_pairs, st));
-            MOSAIC_HIP(hipMemcpyAsync(&n_pairs, d_num.p, 8, hipMemcpyDeviceToHost, st));
-            MOSAIC_HIP(hipStreamSynchronize(st));
-            pairs = d_k1.as<uint64_t>();
-        }
     }
-    nb->n_pairs = n_pairs;
-    const size_t pb = std::max<size_t>((size_t)n_pairs * 8, 16);
-    MOSAIC_HIP(hipMalloc((void**)&nb->left_row, pb));
-    MOSAIC_HIP(hipMalloc((void**)&nb->right_row, pb));
-    MOSAIC_HIP(hipMalloc((void**)&nb->distance, pb));
-    if (n_pairs > 0) {
-        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, pairs, n_pairs, nb->left_row,
-                           nb->right_row);
-        MOSAIC_HIP(hipGetLastError());
-    }
-    MOSAIC_HIP(hipEventRecord(ev.e[1], st));
-    if (n_pairs > 0) MOSAIC_RC(mosaic_st_distance(ctx, left, right, nb->left_row, nb->right_row, n_pairs, nb->distance, nullptr));
-    MOSAIC_HIP(hipEventRecord(ev.e[2], st));
-    if (n_pairs > 0) {
-        // `pairs` is ordered by (landmark, candidate): stable by distance bits, then stable by landmark (the
-        // second sort leaves the distances in the result's own array)
-        Buf d_d1, d_p1;
-        MOSAIC_RC(d_d1.reserve((size_t)n_pairs * 8));
-        MOSAIC_RC(d_p1.reserve((size_t)n_pairs * 8));
-        uint64_t* other = pairs == d_k0.as<uint64_t>() ? d_k1.as<uint64_t>() : d_k0.as<uint64_t>();
-        MOSAIC_RC(dev::sort_pairs(d_tmp, (const uint64_t*)nb->distance, d_d1.as<uint64_t>(), pairs, d_p1.as<uint64_t>(), (int)n_pairs, 0, 64, st));
-        MOSAIC_RC(dev::sort_pairs(d_tmp, d_p1.as<uint64_t>(), other, d_d1.as<uint64_t>(), (uint64_t*)nb->distance, (int)n_pairs, 32, 32 + bits_for(n_left), st));
-        hipLaunchKernelGGL(k_rn_unpack, dim3(blocks_for(n_pairs, kBlock, wide)), dim3(kBlock), 0, st, other, n_pairs, nb->left_row,
-                           nb->right_row);
-        MOSAIC_HIP(hipGetLastError());
-    }
-    MOSAIC_HIP(hipEventRecord(ev.e[3], st));
-    MOSAIC_HIP(hipStreamSynchronize(st));
+    MOSAIC_RC(finish_pairs(ctx, ex, left, right, d_k0, d_k1, n_pairs, keep_self, nullptr, nb.get(), ev));
     for (int i = 0; i < 3; i++) {
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]);
@@ -466,6 +700,93 @@ double mosaic_ring_neighbours_last_ms(double* split3) {
     if (split3)
         for (int i = 0; i < 3; i++) split3[i] = g_last_ms[i];
     return g_last_ms[0] + g_last_ms[1] + g_last_ms[2];
+}
+
+int mosaic_within_candidates(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                             const double* radius, int64_t n, int64_t* counts) {
+    MOSAIC_RC(within_args("within_candidates", ctx, left, right, left_row, radius, n, counts || n == 0));
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    if (left->device != ex.device || right->device != ex.device)
+        return mosaic_tess_fail(MOSAIC_E_ARG, "within_candidates: a geometry column of another device");
+    if (n == 0) return MOSAIC_OK;
+    hipStream_t st = ex.stream;
+    WithinPlan p;
+    MOSAIC_RC(within_count(ctx, ex, "within_candidates", left, right, left_row, radius, n, p));
+    Buf d_out;
+    MOSAIC_RC(d_out.reserve((size_t)n * 8));
+    hipLaunchKernelGGL(k_wn_rowsum, dim3(blocks_for(n, kBlock, (int64_t)ex.n_cu * 16)), dim3(kBlock), 0, st, p.cnt.as<uint64_t>(), n,
+                       p.a.slices, d_out.as<int64_t>());
+    MOSAIC_HIP(hipGetLastError());
+    MOSAIC_HIP(hipMemcpyAsync(counts, d_out.p, (size_t)n * 8, hipMemcpyDefault, st));
+    MOSAIC_HIP(hipStreamSynchronize(st));
+    return MOSAIC_OK;
+}
+
+int mosaic_within_neighbours(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                             const double* radius, int64_t n, int keep_self, mosaic_neighbours** out) {
+    MOSAIC_RC(within_args("within_neighbours", ctx, left, right, left_row, radius, n, out != nullptr));
+    *out = nullptr;
+    dev::Exec ex;
+    MOSAIC_RC(dev::enter(ctx, &ex));
+    if (left->device != ex.device || right->device != ex.device)
+        return mosaic_tess_fail(MOSAIC_E_ARG, "within_neighbours: a geometry column of another device");
+    hipStream_t st = ex.stream;
+    const int64_t n_left = left->n_geoms;
+    g_within_ms[0] = g_within_ms[1] = g_within_ms[2] = 0;
+
+    std::unique_ptr<mosaic_neighbours> nb(new mosaic_neighbours());
+    nb->device = ex.device;
+    nb->n_left = n_left;
+    dev::Events<4> ev;
+    MOSAIC_RC(ev.create());
+    MOSAIC_HIP(hipEventRecord(ev.e[0], st));
+    MOSAIC_HIP(hipMalloc((void**)&nb->unmatched, std::max<size_t>((size_t)n_left, 16)));
+    MOSAIC_HIP(hipMemsetAsync(nb->unmatched, 0, std::max<size_t>((size_t)n_left, 16), st));
+
+    WithinPlan p;
+    Buf d_off, d_tmp, d_k0, d_k1;
+    int64_t total = 0;
+    RadiusSelect sel{nullptr, nullptr, n};
+    if (n > 0) {
+        MOSAIC_RC(within_count(ctx, ex, "within_neighbours", left, right, left_row, radius, n, p));
+        sel.left_row = p.a.left_row;
+        sel.radius = p.a.radius;
+        const int64_t slots = n * p.a.slices;
+        // off[0] = 0, off[j + 1] = cnt[0] + .. + cnt[j]: off[slots] is the number of candidate pairs
+        MOSAIC_RC(d_off.reserve((size_t)(slots + 1) * 8));
+        MOSAIC_HIP(hipMemsetAsync(d_off.p, 0, 8, st));
+        MOSAIC_RC(dev::inclusive_sum(d_tmp, p.cnt.as<uint64_t>(), d_off.as<uint64_t>() + 1, (int)slots, st));
+        uint64_t tot = 0;
+        MOSAIC_HIP(hipMemcpyAsync(&tot, d_off.as<uint64_t>() + slots, 8, hipMemcpyDeviceToHost, st));
+        MOSAIC_HIP(hipStreamSynchronize(st));
+        if (tot >= (uint64_t)rn::kMaxRows)
+            return mosaic_tess_fail(MOSAIC_E_CAPACITY, ("within_neighbours: " + std::to_string(tot) +
+                                                        " candidate pairs in one call, 2^31 - 1 at the most: pass fewer rows").c_str());
+        total = (int64_t)tot;
+    }
+    if (total > 0) {
+        MOSAIC_RC(d_k0.reserve((size_t)total * 8));
+        MOSAIC_RC(d_k1.reserve((size_t)total * 8));
+        p.a.off = d_off.as<uint64_t>();
+        p.a.keys = d_k0.as<uint64_t>();
+        hipLaunchKernelGGL(k_wn_emit, p.grid, dim3(kBlock), p.lds, st, p.a);
+        MOSAIC_HIP(hipGetLastError());
+    }
+    MOSAIC_RC(finish_pairs(ctx, ex, left, right, d_k0, d_k1, total, keep_self, &sel, nb.get(), ev));
+    for (int i = 0; i < 3; i++) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]);
+        g_within_ms[i] = ms;
+    }
+    *out = nb.release();
+    return MOSAIC_OK;
+}
+
+double mosaic_within_neighbours_last_ms(double* split3) {
+    if (split3)
+        for (int i = 0; i < 3; i++) split3[i] = g_within_ms[i];
+    return g_within_ms[0] + g_within_ms[1] + g_within_ms[2];
 }
 
 }  // extern "C"

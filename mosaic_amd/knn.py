@@ -5,7 +5,11 @@ in its ``approximate = true`` form on top of it.
 One iteration (``grid_ring_neighbours``; mosaic_amd/csrc/ring_neighbours.h defines the rows) joins the
 landmarks' ring cells with the candidates' chip cells, keeps one row per (landmark, candidate), drops
 self matches, measures st_distance and orders each landmark's candidates by (distance, candidate row).
-The iteration's bookkeeping (``knn_iterate`` / ``knn_result``) runs in numpy on the exported rows."""
+The iteration's bookkeeping (``knn_iterate`` / ``knn_result``) runs in numpy on the exported rows.
+
+``within_neighbours`` is the distance-within join (all pairs with st_distance <= a per-landmark radius)
+as a second GPU primitive, and ``SpatialKNN.transform_exact`` ranks its rows into every landmark's true
+k nearest (``knn_exact_radius`` / ``knn_exact_batches`` / ``knn_exact_result``, numpy)."""
 import ctypes
 import sys
 
@@ -14,7 +18,8 @@ import numpy as np
 from . import _native as N
 from .context import GeometryTable, _is_torch, tessellate
 
-__all__ = ["CellIndex", "SpatialKNN", "grid_ring_neighbours", "knn_iterate", "knn_result"]
+__all__ = ["CellIndex", "SpatialKNN", "grid_ring_neighbours", "knn_iterate", "knn_result", "within_candidates",
+           "within_neighbours", "knn_exact_radius", "knn_exact_batches", "knn_exact_result"]
 
 
 class CellIndex:
@@ -134,6 +139,96 @@ def ring_neighbours_last_ms():
     return tuple(float(v) for v in split)
 
 
+def _within_args(ctx, landmarks, candidates, radius, rows, own):
+    """the two sides as tables (those built here are appended to ``own``), the rows (or None) and one
+    radius per requested row, on the host or the device"""
+    tabs = []
+    for side in (landmarks, candidates):
+        if not isinstance(side, GeometryTable):
+            side = ctx.geometry_table(side)
+            own.append(side)
+        tabs.append(side)
+    if rows is not None:
+        rows = _index_array(rows)
+        if rows.ndim != 1:
+            raise ValueError("st_dwithin: rows is a 1-d array of landmark rows")
+    n = len(tabs[0]) if rows is None else len(rows)
+    if _is_torch(radius):
+        import torch
+
+        radius = radius.to(torch.float64).contiguous()
+        if radius.dim() == 0:
+            radius = radius.expand(n).contiguous()
+    else:
+        radius = np.asarray(radius, np.float64)
+        radius = np.full(n, float(radius)) if radius.ndim == 0 else np.ascontiguousarray(radius)
+    if radius.ndim != 1 or len(radius) != n:
+        raise ValueError(f"st_dwithin: {len(radius) if radius.ndim == 1 else radius.shape} radii for {n} rows")
+    ctx._order(rows, radius)
+    return tabs, rows, radius, n
+
+
+def within_candidates(ctx, landmarks, candidates, radius, rows=None):
+    """The envelope filter's own count per requested row (mosaic_within_candidates): the candidates that
+    are ROW_OK with at least one facet and whose box bound ``dist::box_lower_bound`` is <= the row's
+    radius; 0 for a landmark that is not such a row and for a NaN or negative radius.  It is at least
+    the number of pairs ``within_neighbours`` returns for the row, and what a caller sizes its calls by.
+    Arguments as for ``within_neighbours``.  Returns int64 counts."""
+    own = []
+    try:
+        tabs, rows, radius, n = _within_args(ctx, landmarks, candidates, radius, rows, own)
+        counts = np.zeros(n, np.int64)
+        N.check(N.lib().mosaic_within_candidates(ctx.handle, tabs[0].handle, tabs[1].handle, N.ptr(rows), N.ptr(radius), n,
+                                                 N.ptr(counts)))
+    finally:
+        for t in own:
+            t.close()
+    return counts
+
+
+def within_neighbours(ctx, landmarks, candidates, radius, rows=None, keep_self=True):
+    """The distance-within join on the context's GPU (mosaic_within_neighbours): all (landmark,
+    candidate) pairs with ``st_distance <= radius`` of the landmark's row.  ``landmarks`` /
+    ``candidates``: ``GeometryTable``s or anything ``geometry_table`` accepts; ``radius``: one number
+    for all rows or one per requested row; ``rows``: the landmark rows asked for, strictly ascending
+    (None: all of them); radius and rows on the host or the device.
+
+    Returns ``(landmark_row, candidate_row, distance)`` ordered by (landmark row, distance, candidate
+    row).  Both rows of a pair are ROW_OK and have at least one facet: an empty geometry is within
+    distance of nothing, null and row-path rows never pair.  A NaN or negative radius gives its row no
+    pairs; ``inf`` accepts every such candidate.  A self match (``grid_ring_neighbours``' exact
+    comparison) is dropped unless ``keep_self``.  The rows are those of the sequential definition over
+    all pairs in mosaic_amd/csrc/ring_neighbours.h (rn::within): the envelope filter that finds the
+    candidates drops none."""
+    own = []
+    h = ctypes.c_void_p()
+    lib = N.lib()
+    try:
+        tabs, rows, radius, n = _within_args(ctx, landmarks, candidates, radius, rows, own)
+        N.check(lib.mosaic_within_neighbours(ctx.handle, tabs[0].handle, tabs[1].handle, N.ptr(rows), N.ptr(radius), n,
+                                             int(bool(keep_self)), ctypes.byref(h)))
+        n_pairs = ctypes.c_int64(0)
+        N.check(lib.mosaic_neighbours_info(h, ctypes.byref(n_pairs), None))
+        l = np.zeros(n_pairs.value, np.int64)
+        c = np.zeros(n_pairs.value, np.int64)
+        d = np.zeros(n_pairs.value, np.float64)
+        N.check(lib.mosaic_neighbours_export(h, N.ptr(l), N.ptr(c), N.ptr(d), None))
+    finally:
+        if h:
+            lib.mosaic_neighbours_destroy(h)
+        for t in own:
+            t.close()
+    return l, c, d
+
+
+def within_neighbours_last_ms():
+    """(envelope filter + self-match filter, distance + radius select, order): device ms of the calling
+    thread's last within_neighbours (HIP events)."""
+    split = np.zeros(3, np.float64)
+    N.lib().mosaic_within_neighbours_last_ms(N.ptr(split))
+    return tuple(float(v) for v in split)
+
+
 def _bits(d):
     return np.ascontiguousarray(d, np.float64).view(np.uint64)
 
@@ -191,6 +286,78 @@ def knn_result(matches, k_neighbours, distance_threshold):
         keep &= d <= distance_threshold
     return dict(landmark_row=l[keep], candidate_row=c[keep], distance=d[keep], iteration=it[keep],
                 neighbour_number=number[keep])
+
+
+def knn_exact_radius(matches, n_landmarks, k_neighbours, distance_threshold):
+    """The radius ``transform_exact`` asks the distance-within join for, per landmark: over the distinct
+    candidates of the match list whose distance is a number <= ``distance_threshold``, the
+    ``k_neighbours``-th smallest distance when there are that many, else ``distance_threshold``.
+    With k candidates within r, a landmark's true k nearest all lie within r.  Returns ``(radius,
+    from_ring)``; ``from_ring[l]`` says that the radius is a k-th ring distance."""
+    l, c, d, _ = matches
+    n = int(n_landmarks)
+    radius = np.full(n, float(distance_threshold), np.float64)
+    from_ring = np.zeros(n, bool)
+    with np.errstate(invalid="ignore"):
+        ok = np.asarray(d, np.float64) <= distance_threshold  # False for NaN
+    l, c, d = np.asarray(l, np.int64)[ok], np.asarray(c, np.int64)[ok], np.asarray(d, np.float64)[ok]
+    if len(l) == 0:
+        return radius, from_ring
+    _, first = np.unique(l << 32 | c, return_index=True)  # a pair's distance is the same in every iteration
+    l, d = l[first], d[first]
+    order = np.lexsort((_bits(d), l))
+    l, d = l[order], d[order]
+    start = np.flatnonzero(np.r_[True, l[1:] != l[:-1]])
+    size = np.diff(np.r_[start, len(l)])
+    full = size >= k_neighbours
+    radius[l[start[full]]] = d[start[full] + k_neighbours - 1]
+    from_ring[l[start[full]]] = True
+    return radius, from_ring
+
+
+def knn_exact_batches(counts, pair_budget):
+    """Consecutive landmarks grouped while their summed candidate counts stay <= ``pair_budget``; a
+    landmark over the budget is a batch of its own.  Returns ``[(first, stop), ...]`` covering
+    ``range(len(counts))``."""
+    batches, first, total = [], 0, 0
+    for i, k in enumerate(np.asarray(counts, np.int64).tolist()):
+        if i > first and total + k > pair_budget:
+            batches.append((first, i))
+            first, total = i, 0
+        total += k
+    if len(counts) > first:
+        batches.append((first, len(counts)))
+    return batches
+
+
+def knn_exact_result(within, matches, active_sets, n_landmarks, k_neighbours):
+    """``transform_exact``'s result from the distance-within rows ``within = (landmark_row,
+    candidate_row, distance)``, ordered by (landmark row, distance bits, candidate row) with each pair
+    once: neighbour_number is the rank in that order and the first ``k_neighbours`` stay.
+    ``iteration`` is the first iteration of the match list that holds the pair, else the landmark's
+    last active iteration + 1 (what the reference's last pass writes)."""
+    l, c, d = (np.asarray(within[0], np.int64), np.asarray(within[1], np.int64), np.asarray(within[2], np.float64))
+    first = np.flatnonzero(np.r_[True, l[1:] != l[:-1]]) if len(l) else np.zeros(0, np.int64)
+    sizes = np.diff(np.r_[first, len(l)])
+    number = (np.arange(len(l)) - np.repeat(first, sizes) + 1).astype(np.int32)
+    keep = number <= k_neighbours
+    l, c, d, number = l[keep], c[keep], d[keep], number[keep]
+    last_active = np.zeros(int(n_landmarks), np.int32)
+    for it, active in enumerate(active_sets, 1):
+        last_active[np.asarray(active, np.int64)] = it
+    iteration = last_active[l] + 1
+    m_l, m_c, _, m_it = matches
+    if len(m_l) and len(l):
+        key = np.asarray(m_l, np.int64) << 32 | np.asarray(m_c, np.int64)
+        order = np.lexsort((m_it, key))
+        key, its = key[order], np.asarray(m_it, np.int32)[order]
+        head = np.r_[True, key[1:] != key[:-1]]
+        key, its = key[head], its[head]  # the first iteration of every matched pair
+        mine = l << 32 | c
+        at = np.minimum(np.searchsorted(key, mine), len(key) - 1)
+        hit = key[at] == mine
+        iteration = np.where(hit, its[at], iteration)
+    return dict(landmark_row=l, candidate_row=c, distance=d, iteration=iteration.astype(np.int32), neighbour_number=number)
 
 
 def _side_kind(geoms, what):
@@ -263,7 +430,9 @@ class SpatialKNN:
     As in the reference, the match list is a list: a candidate with chips both in a landmark's ring 1
     and in its loop 2 is matched in both iterations, both rows count towards k_neighbours and both stay
     in the result.  ``approximate=False`` -- the exact last pass over st_buffer(geometry, k-th distance)
-    -- raises NotImplementedError: the engine has no st_buffer."""
+    -- raises NotImplementedError: the engine has no st_buffer.  ``transform_exact`` is the engine's own
+    exact answer -- every landmark's true k nearest, from the distance-within join -- and says why it
+    is not that pass."""
 
     def __init__(self, ctx, candidates, k_neighbours=5, index_resolution=None, max_iterations=10, early_stop_iterations=3,
                  distance_threshold=sys.float_info.max, approximate=True):
@@ -287,33 +456,81 @@ class SpatialKNN:
         self._index = None
         self._matches = None
         self.active_sets = None
+        self.exact_stats = None  # of the last transform_exact
+        self.exact_radius = None  # the radius it asked for, per landmark
 
     def _prepare(self):
         if self._right is None:
             self._right = _Side(self.ctx, self.candidates, self.index_resolution)
             self._index = CellIndex(self.ctx, (self._right.index_id, self._right.key))
 
+    def _iterate(self, left):
+        """the model's iterations over the landmark side: the match list and the active sets"""
+        ctx = self.ctx
+        res = self.index_resolution
+
+        def step(active, it):
+            rings = ctx._geometry_kring(left.chips_of(active), res, it, it > 1, True)
+            lens = np.fromiter((len(r) for r in rings), np.int64, len(rings))
+            rows = np.repeat(active, lens)
+            cells = np.concatenate(rings) if len(rings) else np.zeros(0, np.int64)
+            return grid_ring_neighbours(ctx, left.table, self._right.table, self._index, rows, cells)
+
+        return knn_iterate(left.n, step, self.k_neighbours, self.max_iterations, self.early_stop_iterations,
+                           self.distance_threshold)
+
     def transform(self, landmarks):
         """The matches as columns ``landmark_row``, ``candidate_row``, ``distance``, ``iteration`` and
         ``neighbour_number`` (a dict of arrays), ordered by (landmark row, neighbour number)."""
         _side_kind(landmarks, "the landmarks")
         self._prepare()
-        ctx = self.ctx
-        res = self.index_resolution
-        left = _Side(ctx, landmarks, res)
+        left = _Side(self.ctx, landmarks, self.index_resolution)
         try:
-            def step(active, it):
-                rings = ctx._geometry_kring(left.chips_of(active), res, it, it > 1, True)
-                lens = np.fromiter((len(r) for r in rings), np.int64, len(rings))
-                rows = np.repeat(active, lens)
-                cells = np.concatenate(rings) if len(rings) else np.zeros(0, np.int64)
-                return grid_ring_neighbours(ctx, left.table, self._right.table, self._index, rows, cells)
-
-            matches, self.active_sets = knn_iterate(left.n, step, self.k_neighbours, self.max_iterations,
-                                                    self.early_stop_iterations, self.distance_threshold)
+            matches, self.active_sets = self._iterate(left)
         finally:
             left.close()
         self._matches = knn_result(matches, self.k_neighbours, self.distance_threshold)
+        return self._matches
+
+    def transform_exact(self, landmarks, pair_budget=1 << 24):
+        """Every landmark's true ``k_neighbours`` nearest candidates within ``distance_threshold``, by
+        (distance, candidate row), self matches excluded: the columns of ``transform``, each (landmark,
+        candidate) once, what a brute force over all pairs returns.
+
+        The iterations of ``transform`` run first.  A landmark whose match list holds k distinct
+        candidates within the threshold gets their k-th distance as its radius (``knn_exact_radius``),
+        any other landmark the threshold; the distance-within join (``within_neighbours``,
+        ``keep_self=False``) over those radii returns a superset of the k nearest, which is ranked.
+        The join runs in batches of consecutive landmarks whose candidate pairs
+        (``within_candidates``) sum to at most ``pair_budget``; a landmark over the budget is a batch
+        of its own.  ``iteration`` is the first iteration that matched the pair, else the landmark's
+        last active iteration + 1.  ``exact_stats`` reports landmarks with a ring radius and with the
+        threshold radius, batches, candidate pairs and pairs within; ``metrics()`` serves the result.
+
+        This is the engine's own exact answer, not the reference's ``approximate = false`` pass: that
+        pass tessellates st_buffer(geometry, k-th distance), revisits only the landmarks still active
+        after the last iteration and appends to the match list, so it is neither de-duplicated nor
+        exact for the others.  Here every landmark is revisited, the result is de-duplicated, and no
+        buffer polygon is involved."""
+        _side_kind(landmarks, "the landmarks")
+        self._prepare()
+        ctx = self.ctx
+        left = _Side(ctx, landmarks, self.index_resolution)
+        try:
+            matches, self.active_sets = self._iterate(left)
+            radius, from_ring = knn_exact_radius(matches, left.n, self.k_neighbours, self.distance_threshold)
+            counts = within_candidates(ctx, left.table, self._right.table, radius)
+            batches = knn_exact_batches(counts, pair_budget)
+            parts = [within_neighbours(ctx, left.table, self._right.table, radius[a:b], rows=np.arange(a, b, dtype=np.int64),
+                                       keep_self=False) for a, b in batches]
+        finally:
+            left.close()
+        within = tuple(np.concatenate([p[i] for p in parts]) if parts else np.zeros(0, t)
+                       for i, t in enumerate((np.int64, np.int64, np.float64)))
+        self.exact_radius = radius
+        self.exact_stats = dict(ring_radius=int(from_ring.sum()), threshold_radius=int((~from_ring).sum()), batches=len(batches),
+                                candidate_pairs=int(counts.sum()), pairs_within=len(within[0]))
+        self._matches = knn_exact_result(within, matches, self.active_sets, left.n, self.k_neighbours)
         return self._matches
 
     def metrics(self):
