@@ -745,6 +745,33 @@ int mosaic_st_intersects(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic
 /* the calling thread's last mosaic_st_intersects: pairs ended in the plan kernel (null, row-path, empty
  * or box-disjoint), pairs served by one lane, pairs served by a workgroup (any may be null) */
 int mosaic_st_intersects_last_split(int64_t* ended_in_plan, int64_t* one_lane, int64_t* workgroup);
+/* out[i] = st_contains(left[left_row[i]], right[right_row[i]]) as 1 or 0 (ST_Contains.scala ->
+ * MosaicGeometryJTS.contains -> JTS Geometry.contains, DE-9IM T*****FF*: no point of the right geometry
+ * lies in the exterior of the left one and the interiors share a point), for any two of the row kinds
+ * mosaic_st_distance serves; left_row == right_row == NULL: row i with row i.  st_within(b, a) is the
+ * same call with the sides swapped.  Value and status are those of the sequential definition in
+ * mosaic_amd/csrc/st_contains.h, which decides on exact predicates only and constructs no point:
+ * 0 when either geometry is empty or the right box is not inside the left box; points against a
+ * polygonal or a points-only left side are located one by one; a line or polygon against a polygonal
+ * left side is 0 on a proper crossing or an exterior vertex, and decided by first vertices when no
+ * facets meet.
+ * status[i] (nullable): MOSAIC_ROW_OK: out is the answer.  MOSAIC_ROW_NULL / MOSAIC_ROW_PATH as for
+ * mosaic_st_distance, out 0.  MOSAIC_PAIR_UNDECIDED, out 0: both rows are served, but this pair is left
+ * to the caller's row-wise expression -- the boundaries touch without crossing and no vertex is
+ * outside, or the left side has line parts, or it is points only and the right side is not.  It is a
+ * property of the pair, where MOSAIC_ROW_PATH is one of a row.
+ * A row index out of range: MOSAIC_E_ARG, nothing written.  out / status / the row arrays: host or
+ * device pointers.  Options: "dist_tile" and "dist_small_work" as for mosaic_st_intersects.
+ * mosaic_st_contains (polygon contains POINT (x y) from WKB) is untouched. */
+#define MOSAIC_PAIR_UNDECIDED 3
+int mosaic_st_contains_geoms(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
+                             const int64_t* right_row, int64_t n_pairs, uint8_t* out, int32_t* status);
+/* the calling thread's last mosaic_st_contains_geoms, five counts that add up to its pairs except the
+ * last: [0] ended in the plan kernel with a status other than MOSAIC_PAIR_UNDECIDED (null, row-path,
+ * empty, box-rejected, or points decided there); [1] served by a later kernel and decided by a proper
+ * crossing, an exterior vertex or an exterior point; [2] served by a later kernel and decided without
+ * contact, or points all located; [3] MOSAIC_PAIR_UNDECIDED; [4] of all these, served by a workgroup */
+int mosaic_st_contains_last_split(int64_t out5[5]);
 /* The measures of one geometry per row (ST_Area, ST_Length = ST_Perimeter, ST_Centroid, ST_NumPoints,
  * ST_XMin .. ST_YMax -> MosaicGeometryJTS -> JTS 1.19 getArea / getLength / getCentroid /
  * getNumPoints): output row i describes geoms[rows[i]], rows == NULL: row i (n <= the column's rows).

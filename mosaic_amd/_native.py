@@ -55,6 +55,7 @@ EXPORTS = [
     "mosaic_line_intersection_aggregate", "mosaic_line_intersection_aggregate_geometry",
     "mosaic_line_intersection_last", "mosaic_line_intersection_aggregate_host",
     "mosaic_st_intersects", "mosaic_st_intersects_last_split",
+    "mosaic_st_contains_geoms", "mosaic_st_contains_last_split",
     "mosaic_st_measures", "mosaic_st_measures_last_split",
     "mosaic_within_candidates", "mosaic_within_neighbours", "mosaic_within_neighbours_last_ms",
 ]
@@ -66,6 +67,7 @@ GEOM_OFFSETS32 = 0x100
 ROW_NULL = 0
 ROW_OK = 1
 ROW_PATH = 2
+PAIR_UNDECIDED = 3  # mosaic_st_contains_geoms: a pair of served rows that is left to the row-wise expression
 GEOMS_LINES = 1  # mosaic_geoms_create_wkb_ex: decode LineString / MultiLineString rows
 
 
@@ -194,6 +196,8 @@ def lib():
         "mosaic_st_distance": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
         "mosaic_st_intersects": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
         "mosaic_st_intersects_last_split": ([ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "mosaic_st_contains_geoms": ([vp, vp, vp, vp, vp, i64, vp, vp], i32),
+        "mosaic_st_contains_last_split": ([vp], i32),
         "mosaic_st_measures": ([vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mosaic_st_measures_last_split": ([ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "mosaic_cell_index_create": ([vp, i64, vp, vp, ctypes.POINTER(vp)], i32),

@@ -964,6 +964,35 @@ class MosaicContext:
         res = self._pair_call("st_intersects", N.lib().mosaic_st_intersects, np.uint8, left, right, pairs, return_status)
         return (res[0].astype(bool), res[1]) if return_status else res.astype(bool)
 
+    def st_contains_geoms(self, left, right, pairs=None, return_status=False):
+        """st_contains(left, right) over any two geometries (expressions/geometry/ST_Contains.scala ->
+        core/geometry/MosaicGeometryJTS.contains -> JTS 1.19 Geometry.contains, DE-9IM T*****FF*) on this
+        context's GPU (mosaic_st_contains_geoms): no point of the right geometry lies in the exterior of
+        the left one, and the interiors share a point -- value and status of the sequential definition
+        in mosaic_amd/csrc/st_contains.h, which decides on exact predicates only.  Point, MultiPoint,
+        LineString, MultiLineString, Polygon and MultiPolygon rows are served on either side.
+        ``st_contains(geoms, points)`` is the older form for polygons from WKB against point columns.
+
+        Arguments as for ``st_intersects``.  Returns a bool array, False on null rows.  A pair the
+        engine does not decide has the status ``PAIR_UNDECIDED`` (the boundaries touch without
+        crossing and no vertex is outside, or the left side is not polygonal and the right side is
+        not points only): both rows are served, but this pair goes to the reference's row-wise
+        expression.  Such pairs, and rows either side leaves to the row path, raise
+        ``RowPathRequired`` with the pair indices, unless return_status, which adds the pairs' status
+        array (ROW_OK / ROW_NULL / ROW_PATH / PAIR_UNDECIDED; False wherever it is not ROW_OK)."""
+        out, status = self._pair_call("st_contains", N.lib().mosaic_st_contains_geoms, np.uint8, left, right, pairs, True)
+        if return_status:
+            return out.astype(bool), status
+        rest = np.flatnonzero((status == N.ROW_PATH) | (status == N.PAIR_UNDECIDED))
+        if len(rest):
+            raise RowPathRequired(rest)
+        return out.astype(bool)
+
+    def st_within_geoms(self, left, right, pairs=None, return_status=False):
+        """st_within(left, right) = st_contains(right, left) (JTS Geometry.within): ``st_contains_geoms``
+        with the sides swapped; ``pairs=(left_idx, right_idx)`` name (left row, right row) as given."""
+        return self.st_contains_geoms(right, left, None if pairs is None else (pairs[1], pairs[0]), return_status)
+
     # ---- one geometry per row: area, length, centroid, numpoints, bounds ----
     MEASURES = ("area", "length", "centroid", "numpoints", "xmin", "ymin", "xmax", "ymax")
 
