@@ -107,6 +107,30 @@ int on_device(const T* src, int64_t n, Buf& stage, hipStream_t stream, const T**
     return MOSAIC_OK;
 }
 
+// one output array of n elements: the caller's if it is on the device (or null), else a staging block
+// that back() copies to the caller at the end
+template <class T>
+struct OutSlot {
+    T* user = nullptr;
+    T* dev = nullptr;
+    Buf stage;
+    int bind(T* p, int64_t n) {
+        user = p;
+        if (!p) return MOSAIC_OK;
+        if (is_device_ptr(p)) {
+            dev = p;
+            return MOSAIC_OK;
+        }
+        MOSAIC_RC(stage.reserve((size_t)n * sizeof(T)));
+        dev = (T*)stage.p;
+        return MOSAIC_OK;
+    }
+    int back(int64_t n, hipStream_t stream) {
+        if (user && user != dev) MOSAIC_HIP(hipMemcpyAsync(user, dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
+        return MOSAIC_OK;
+    }
+};
+
 // N timing events, destroyed on every return path
 template <int N>
 struct Events {

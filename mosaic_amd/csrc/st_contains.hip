@@ -6,7 +6,7 @@
 // st_distance.hip.
 //
 // Per call:
-//   k_cont_plan    one lane per pair: row range check and row status as in k_isect_plan, then steps 1, 2
+//   k_cont_plan    one lane per pair: row range check and row status (pairs::plan_status), then steps 1, 2
 //                  and 6 of the definition (a side without facets, B's box not inside A's, a left side
 //                  that is not polygonal): such a pair ends here.  So does a points-only B (steps 3 and
 //                  4) of at most dist_small_work facet pairs, decided by this lane.  The others go by
@@ -16,13 +16,12 @@
 //   k_cont_fill    status[] and out[] of every pair from plan[]
 //   k_cont_small   one lane per pair: the sequential driver contains::contains_how
 //   k_cont_block   one workgroup per pair.
-//                  Step 5: A's segments are staged in LDS, a tile of dist_tile segments at a time, B's
-//                  are streamed across the lanes; a staged ring, a tile, a (tile, streamed ring) or a
-//                  (tile, streamed segment) block whose boxes do not meet is skipped exactly as in
-//                  k_isect_block.  Unlike there the sweep does not stop at the first contact: it sets
-//                  `contact` and goes on, and stops at the first proper crossing (an LDS flag every lane
-//                  reads before each streamed segment and the workgroup at every tile).  Then the
-//                  location phase, for the pairs without a crossing: with contact every vertex of B is
+//                  Step 5: pairs::sweep_tiles stages A's segments in LDS, a tile of dist_tile segments at
+//                  a time, streams B's across the lanes and skips the blocks whose boxes do not meet.
+//                  Unlike k_isect_block's, the body given to it here does not stop at the first contact:
+//                  it sets `contact` and goes on, and stops at the first proper crossing (the sweep's
+//                  stop flag: every lane reads it before each streamed segment, the workgroup at every
+//                  tile).  Then the location phase, for the pairs without a crossing: with contact every vertex of B is
 //                  located in A, one wave per vertex, until one is EXTERIOR; without contact the first
 //                  vertices of 5(c), one wave per (part of B) and per (ring of A, polygon part of B).
 //                  The locate is the wave-cooperative one of pip_coop.h: lanes over the ring's segments,
@@ -30,9 +29,8 @@
 //                  Steps 3 and 4 beyond dist_small_work: one wave per point of B against A's parts, or
 //                  one lane per point of B against A's points.
 // All results are written with ordinary vector stores; the split counts are atomic adds.
-#include "dev_rt.h"
 #include "geoms_device.h"
-#include "pair_lists.h"
+#include "pair_call.h"
 #include "pip_coop.h"
 #include "st_contains.h"
 
@@ -40,78 +38,50 @@ using namespace mosaic;
 
 namespace {
 
-using dev::blocks_for;
-using dev::Buf;
-using dev::is_device_ptr;
-using pairs::Col;
 using pairs::kBlock;
-using pairs::view;
-using pairs::wave_append;
-constexpr int kMaxTile = 1024;
+using pairs::kMaxTile;
 constexpr int kWaves = kBlock / 64;
 
-// counters of a call
-enum { kCntSmall = 0, kCntBlock = 1, kCntBadRow = 2, kCntKinds = 3, kCntOut = 4, kCntClear = 5, kCntTouch = 6, kCounters = 8 };
+// counters of a call, above pairs::kCntSmall / kCntBlock / kCntBadRow
+enum { kCntKinds = 3, kCntOut = 4, kCntClear = 5, kCntTouch = 6, kCounters = 8 };
 
 // the last call of this thread: ended in plan, decided by a crossing or an exterior vertex, decided
 // without contact, undecided, served by a workgroup
 thread_local int64_t t_last[5] = {0, 0, 0, 0, 0};
 
-struct PlanArgs {
-    Col L, R;
-    const int64_t *lrow, *rrow;  // both null: pair i is (row i, row i)
-    int64_t n;
-    unsigned long long small_work;
-    int32_t* plan;               // the pair's status | out << 8; -1: a row index out of range
-    int64_t* list;               // small pairs from the front, block pairs from the back
-    unsigned long long* counts;  // kCnt*
-};
-
-__global__ void __launch_bounds__(kBlock) k_cont_plan(PlanArgs a) {
+// plan[i] here: the pair's status | out << 8
+__global__ void __launch_bounds__(kBlock) k_cont_plan(pairs::PlanArgs a) {
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < a.n; i0 += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = i0 + threadIdx.x;
         bool small = false, block = false;
         if (i < a.n) {
-            const int64_t g = a.lrow ? a.lrow[i] : i, h = a.rrow ? a.rrow[i] : i;
-            if (g < 0 || g >= a.L.n || h < 0 || h >= a.R.n) {
-                atomicAdd(&a.counts[kCntBadRow], 1ull);
-                a.plan[i] = -1;
-            } else {
-                const int32_t sl = a.L.status[g], sr = a.R.status[h];
-                int32_t st = MOSAIC_ROW_OK;
-                if (sl == MOSAIC_ROW_NULL || sr == MOSAIC_ROW_NULL)
-                    st = MOSAIC_ROW_NULL;
-                else if (sl != MOSAIC_ROW_OK || sr != MOSAIC_ROW_OK)
-                    st = MOSAIC_ROW_PATH;
-                int32_t out = 0;
-                if (st == MOSAIC_ROW_OK) {
-                    const unsigned long long work = (unsigned long long)a.L.facets[g] * a.R.facets[h];
-                    // steps 1 and 2 of the definition: 0, and the pair reaches no other kernel
-                    if (work != 0 && contains::box_covers(a.L.s.geom_bbox[g], a.R.s.geom_bbox[h])) {
-                        const uint32_t A = contains::geom_kinds(a.L.s, a.L.part_kind, (uint32_t)g);
-                        const uint32_t B = contains::geom_kinds(a.R.s, a.R.part_kind, (uint32_t)h);
-                        const bool points = B == contains::kHasPoint && (A == contains::kHasPolygon || A == contains::kHasPoint);
-                        if (!points && A != contains::kHasPolygon) {  // step 6
-                            st = MOSAIC_PAIR_UNDECIDED;
-                            atomicAdd(&a.counts[kCntKinds], 1ull);
-                        } else if (points && work <= a.small_work) {  // steps 3 and 4
-                            int how;
-                            out = (A == contains::kHasPolygon ? contains::points_in_polygonal(a.L.s, (uint32_t)g, a.R.s, (uint32_t)h, &how)
-                                                              : contains::points_in_points(a.L.s, (uint32_t)g, a.R.s, (uint32_t)h, &how))
-                                      ? 1 : 0;
-                        } else {
-                            small = work <= a.small_work;
-                            block = !small;
-                        }
+            int64_t g, h;
+            int32_t st = pairs::plan_status(a, i, g, h);
+            int32_t out = 0;
+            if (st == MOSAIC_ROW_OK) {
+                const unsigned long long work = (unsigned long long)a.L.facets[g] * a.R.facets[h];
+                // steps 1 and 2 of the definition: 0, and the pair reaches no other kernel
+                if (work != 0 && contains::box_covers(a.L.s.geom_bbox[g], a.R.s.geom_bbox[h])) {
+                    const uint32_t A = contains::geom_kinds(a.L.s, a.L.part_kind, (uint32_t)g);
+                    const uint32_t B = contains::geom_kinds(a.R.s, a.R.part_kind, (uint32_t)h);
+                    const bool points = B == contains::kHasPoint && (A == contains::kHasPolygon || A == contains::kHasPoint);
+                    if (!points && A != contains::kHasPolygon) {  // step 6
+                        st = MOSAIC_PAIR_UNDECIDED;
+                        atomicAdd(&a.counts[kCntKinds], 1ull);
+                    } else if (points && work <= a.small_work) {  // steps 3 and 4
+                        int how;
+                        out = (A == contains::kHasPolygon ? contains::points_in_polygonal(a.L.s, (uint32_t)g, a.R.s, (uint32_t)h, &how)
+                                                          : contains::points_in_points(a.L.s, (uint32_t)g, a.R.s, (uint32_t)h, &how))
+                                  ? 1 : 0;
+                    } else {
+                        small = work <= a.small_work;
+                        block = !small;
                     }
                 }
-                a.plan[i] = st | (out << 8);
             }
+            a.plan[i] = st | (out << 8);  // -1 stays -1
         }
-        const unsigned long long ps = wave_append(&a.counts[kCntSmall], small);
-        const unsigned long long pb = wave_append(&a.counts[kCntBlock], block);
-        if (small) a.list[ps] = i;
-        if (block) a.list[a.n - 1 - (int64_t)pb] = i;
+        pairs::plan_append(a, i, small, block);
     }
 }
 
@@ -123,11 +93,7 @@ __global__ void __launch_bounds__(kBlock) k_cont_fill(const int32_t* plan, int64
     }
 }
 
-struct ContArgs {
-    Col L, R;
-    const int64_t *lrow, *rrow;
-    const int64_t* list;
-    int64_t n_list;
+struct ContArgs : pairs::ListArgs {
     uint8_t* out;
     int32_t* status;  // nullable
     unsigned long long* counts;
@@ -142,7 +108,8 @@ __device__ inline int how_counter(int how) {
 __global__ void __launch_bounds__(kBlock) k_cont_small(ContArgs a) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n_list; k += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = a.list[k];
-        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        uint32_t g, h;
+        pairs::pair_rows(a, i, g, h);
         int32_t st;
         int how;
         a.out[i] = contains::contains_how(a.L.s, a.L.part_kind, g, a.R.s, a.R.part_kind, h, &st, &how);
@@ -171,19 +138,19 @@ __device__ inline bool coop_exterior(const pip::GeomStore& s, uint32_t g, double
 __global__ void __launch_bounds__(kBlock) k_cont_block(ContArgs a) {
     __shared__ pip::Vec2 s_v[kMaxTile + 1];
     __shared__ pip::Box s_box;
-    // s_contact, s_crossed: the sweep; s_out: an exterior vertex or point; s_in: an interior point (step 3);
-    // s_fail: a first-vertex test of 5(c) failed
-    // The flags are set with plain stores and polled through volatile reads without a fence: a poll only
-    // ends a loop early, and every read that decides the result sits behind a __syncthreads.
+    // s_contact, s_crossed: the sweep (s_crossed is its stop flag); s_out: an exterior vertex or point;
+    // s_in: an interior point (step 3); s_fail: a first-vertex test of 5(c) failed
+    // As in pairs::sweep_tiles, the flags are set with plain stores and polled through volatile reads without
+    // a fence: a poll only ends a loop early, and every read that decides the result sits behind a __syncthreads.
     __shared__ int s_contact, s_crossed, s_snap, s_out, s_in, s_fail;
     const uint32_t tid = threadIdx.x;
     const uint32_t wave = tid >> 6;
-    const uint32_t T = (uint32_t)a.tile;
     const pip::GeomStore& SA = a.L.s;
     const pip::GeomStore& SB = a.R.s;
     for (int64_t k = blockIdx.x; k < a.n_list; k += gridDim.x) {
         const int64_t i = a.list[k];
-        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        uint32_t g, h;
+        pairs::pair_rows(a, i, g, h);
         __syncthreads();  // the previous pair's readers of the flags are done
         if (tid == 0) s_contact = s_crossed = s_out = s_in = s_fail = 0;
         uint32_t ra0, ra1, rb0, rb1;
@@ -224,68 +191,16 @@ __global__ void __launch_bounds__(kBlock) k_cont_block(ContArgs a) {
             out = !s_out && s_in ? 1 : 0;
         } else {
             // ---- step 5(a) and the contact of 5(c): the sweep ----
-            const pip::Box bbox = SB.geom_bbox[h];
-            bool done = false;
-            for (uint32_t ra = ra0; ra < ra1 && !done; ra++) {
-                const uint32_t v0 = SA.ring_start[ra], n = SA.ring_start[ra + 1] - v0;
-                const uint32_t nf = dist::ring_facets(n);
-                if (nf == 0 || !pip::boxes_meet(SA.ring_bbox[ra], bbox)) continue;  // uniform
-                for (uint32_t f0 = 0; f0 < nf; f0 += T) {
-                    const uint32_t cnt = nf - f0 < T ? nf - f0 : T;
-                    __syncthreads();  // the previous tile's readers of s_v / s_box / s_snap are done; the zeroed flags are visible
-                    for (uint32_t t = tid; t <= cnt; t += kBlock) {
-                        const uint32_t vi = f0 + t < n ? f0 + t : n - 1;
-                        s_v[t] = SA.verts[v0 + vi];
-                    }
-                    if (tid == 0) s_snap = *(volatile int*)&s_crossed;
-                    __syncthreads();
-                    if (s_snap) {  // uniform: a proper crossing ends the sweep
-                        done = true;
-                        break;
-                    }
-                    if (tid < 64) {
-                        pip::Box b = {INFINITY, INFINITY, -INFINITY, -INFINITY};
-                        for (uint32_t t = tid; t <= cnt; t += 64) {
-                            const pip::Vec2 v = s_v[t];
-                            b.minx = fmin(b.minx, v.x);
-                            b.miny = fmin(b.miny, v.y);
-                            b.maxx = fmax(b.maxx, v.x);
-                            b.maxy = fmax(b.maxy, v.y);
-                        }
-                        for (int off = 32; off; off >>= 1) {
-                            b.minx = fmin(b.minx, __shfl_xor(b.minx, off, 64));
-                            b.miny = fmin(b.miny, __shfl_xor(b.miny, off, 64));
-                            b.maxx = fmax(b.maxx, __shfl_xor(b.maxx, off, 64));
-                            b.maxy = fmax(b.maxy, __shfl_xor(b.maxy, off, 64));
-                        }
-                        if (tid == 0) s_box = b;
-                    }
-                    __syncthreads();
-                    const pip::Box tb = s_box;
-                    if (!pip::boxes_meet(tb, bbox)) continue;  // uniform
-                    for (uint32_t rb = rb0; rb < rb1; rb++) {
-                        const uint32_t w0 = SB.ring_start[rb], nw = SB.ring_start[rb + 1] - w0;
-                        const uint32_t nfw = dist::ring_facets(nw);
-                        if (nfw == 0 || !pip::boxes_meet(tb, SB.ring_bbox[rb])) continue;
-                        for (uint32_t j = tid; j < nfw; j += kBlock) {
-                            if (*(volatile int*)&s_crossed) break;
-                            pip::Vec2 C, D;
-                            dist::ring_facet(SB.verts + w0, nw, j, C, D);
-                            if (!pip::boxes_meet(tb, isect::facet_box(C, D))) continue;
-                            int worst = 0;
-                            for (uint32_t t = 0; t < cnt && worst < 2; t++) {
-                                const int c = contains::facet_contact(s_v[t], s_v[t + 1], C, D);
-                                worst = c > worst ? c : worst;
-                            }
-                            if (worst) s_contact = 1;
-                            if (worst == 2) {
-                                s_crossed = 1;
-                                break;
-                            }
-                        }
-                    }
-                }
-            }
+            pairs::sweep_tiles(SA, ra0, ra1, SB, rb0, rb1, SB.geom_bbox[h], (uint32_t)a.tile, s_v, &s_box, &s_crossed, &s_snap,
+                               [](const pip::Vec2* v, uint32_t cnt, pip::Vec2 C, pip::Vec2 D) {
+                                   int worst = 0;
+                                   for (uint32_t t = 0; t < cnt && worst < 2; t++) {
+                                       const int c = contains::facet_contact(v[t], v[t + 1], C, D);
+                                       worst = c > worst ? c : worst;
+                                   }
+                                   if (worst) s_contact = 1;
+                                   return worst == 2;
+                               });
             __syncthreads();
             const bool crossed = s_crossed != 0, contact = s_contact != 0;  // uniform: every write of the sweep is behind the barrier
             // ---- the location phase ----
@@ -348,81 +263,33 @@ extern "C" {
 
 int mosaic_st_contains_geoms(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
                              const int64_t* right_row, int64_t n_pairs, uint8_t* out, int32_t* status) {
-    if (!ctx || !left || !right || n_pairs < 0 || (n_pairs > 0 && !out))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
-    if ((left_row == nullptr) != (right_row == nullptr))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_contains: left_row and right_row are both given or both null");
-    if (!left_row && (n_pairs > left->n_geoms || n_pairs > right->n_geoms))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_contains: row-wise form with more pairs than rows");
-    int tile = 16, prune = 1;
-    int64_t small_work = 512;
-    dev::Exec ex;
-    MOSAIC_RC(dev::enter(ctx, &ex));
-    MOSAIC_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
-    if (left->device != ex.device || right->device != ex.device)
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_contains: a geometry column of another device");
+    pairs::Call<uint8_t> c;
+    MOSAIC_RC(c.open("st_contains", ctx, left, right, left_row, right_row, n_pairs, out));
     for (int64_t& v : t_last) v = 0;
     if (n_pairs == 0) return MOSAIC_OK;
-    tile = std::max(1, std::min(tile, kMaxTile));
-    hipStream_t stream = ex.stream;
-    const int64_t n = n_pairs;
-
-    Buf s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
-    PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
-    if (left_row) {
-        MOSAIC_RC(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
-        MOSAIC_RC(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
-    }
-    MOSAIC_RC(s_plan.reserve((size_t)n * sizeof(int32_t)));
-    MOSAIC_RC(s_list.reserve((size_t)n * sizeof(int64_t)));
-    MOSAIC_RC(s_counts.reserve(kCounters * sizeof(unsigned long long)));
-    MOSAIC_HIP(hipMemsetAsync(s_counts.p, 0, kCounters * sizeof(unsigned long long), stream));
-    pa.plan = (int32_t*)s_plan.p;
-    pa.list = (int64_t*)s_list.p;
-    pa.counts = (unsigned long long*)s_counts.p;
-    const int64_t wide = (int64_t)ex.n_cu * 16;
-    hipLaunchKernelGGL(k_cont_plan, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa);
+    MOSAIC_RC(c.stage(kCounters));
+    hipLaunchKernelGGL(k_cont_plan, c.lanes(c.n), dim3(kBlock), 0, c.stream, c.pa);
     MOSAIC_HIP(hipGetLastError());
-    unsigned long long counts[kCounters] = {};
-    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    MOSAIC_HIP(hipStreamSynchronize(stream));
-    if (counts[kCntBadRow])
-        return mosaic_tess_fail(MOSAIC_E_ARG, ("st_contains: " + std::to_string(counts[kCntBadRow]) + " pair(s) name a row outside their column").c_str());
-
-    const bool dev_out = is_device_ptr(out), dev_status = !status || is_device_ptr(status);
-    uint8_t* d_out = out;
-    int32_t* d_status = status;
-    if (!dev_out) {
-        MOSAIC_RC(s_out.reserve((size_t)n));
-        d_out = (uint8_t*)s_out.p;
-    }
-    if (!dev_status) {
-        MOSAIC_RC(s_status.reserve((size_t)n * sizeof(int32_t)));
-        d_status = (int32_t*)s_status.p;
-    }
-    hipLaunchKernelGGL(k_cont_fill, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
+    MOSAIC_RC(c.planned());
+    MOSAIC_RC(c.bind(out, status));
+    hipLaunchKernelGGL(k_cont_fill, c.lanes(c.n), dim3(kBlock), 0, c.stream, c.pa.plan, c.n, c.out.dev, c.status.dev);
     MOSAIC_HIP(hipGetLastError());
-    const int64_t n_small = (int64_t)counts[kCntSmall], n_block = (int64_t)counts[kCntBlock];
-    ContArgs ca{pa.L, pa.R, pa.lrow, pa.rrow, pa.list, n_small, d_out, d_status, pa.counts, tile};
-    if (n_small) {
-        hipLaunchKernelGGL(k_cont_small, dim3((unsigned)blocks_for(n_small, kBlock, wide)), dim3(kBlock), 0, stream, ca);
+    if (c.n_small()) {
+        hipLaunchKernelGGL(k_cont_small, c.lanes(c.n_small()), dim3(kBlock), 0, c.stream,
+                           ContArgs{c.small_list(), c.out.dev, c.status.dev, c.pa.counts, c.tile});
         MOSAIC_HIP(hipGetLastError());
     }
-    if (n_block) {
-        ca.list = pa.list + (n - n_block);
-        ca.n_list = n_block;
-        hipLaunchKernelGGL(k_cont_block, dim3((unsigned)std::min<int64_t>(n_block, (int64_t)1 << 20)), dim3(kBlock), 0, stream, ca);
+    if (c.n_block()) {
+        hipLaunchKernelGGL(k_cont_block, c.groups(c.n_block()), dim3(kBlock), 0, c.stream,
+                           ContArgs{c.block_list(), c.out.dev, c.status.dev, c.pa.counts, c.tile});
         MOSAIC_HIP(hipGetLastError());
     }
-    if (!dev_out) MOSAIC_HIP(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, stream));
-    if (!dev_status) MOSAIC_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (n_small || n_block) MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    MOSAIC_HIP(hipStreamSynchronize(stream));
-    t_last[0] = n - n_small - n_block - (int64_t)counts[kCntKinds];
-    t_last[1] = (int64_t)counts[kCntOut];
-    t_last[2] = (int64_t)counts[kCntClear];
-    t_last[3] = (int64_t)counts[kCntKinds] + (int64_t)counts[kCntTouch];
-    t_last[4] = n_block;
+    MOSAIC_RC(c.finish(c.n_small() || c.n_block()));  // the small and block kernels count how each pair was decided
+    t_last[0] = c.n - c.n_small() - c.n_block() - (int64_t)c.counts[kCntKinds];
+    t_last[1] = (int64_t)c.counts[kCntOut];
+    t_last[2] = (int64_t)c.counts[kCntClear];
+    t_last[3] = (int64_t)c.counts[kCntKinds] + (int64_t)c.counts[kCntTouch];
+    t_last[4] = c.n_block();
     return MOSAIC_OK;
 }
 

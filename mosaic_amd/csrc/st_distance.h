@@ -132,6 +132,9 @@ MOSAIC_HD void ring_facet(const Vec2* v, uint32_t n, uint32_t i, Vec2& A, Vec2& 
     A = v[i];
     B = v[i + 1 < n ? i + 1 : i];
 }
+MOSAIC_HD Box facet_box(Vec2 a, Vec2 b) {
+    return Box{a.x < b.x ? a.x : b.x, a.y < b.y ? a.y : b.y, a.x > b.x ? a.x : b.x, a.y > b.y ? a.y : b.y};
+}
 MOSAIC_HD void geom_rings(const GeomStore& s, uint32_t g, uint32_t& r0, uint32_t& r1) {
     r0 = s.part_ring[s.geom_part[g]];
     r1 = s.part_ring[s.geom_part[g + 1]];

@@ -12,17 +12,19 @@
 // segment, and only polygon parts are containers.
 //
 // Per call:
-//   k_dist_plan    one lane per pair: row range check, row status, work = facets(left) x facets(right);
-//                  pair ids with work <= dist_small_work are appended to the front of one list, the
-//                  others to its back (one atomicAdd per wave and list)
+//   k_dist_plan    one lane per pair: row range check and row status (pairs::plan_status), work =
+//                  facets(left) x facets(right); pair ids with work <= dist_small_work are appended to the
+//                  front of one list, the others to its back (pairs::plan_append: one atomicAdd per wave
+//                  and list)
 //   k_dist_fill    status[] of every pair, NaN for the null / row-path ones (only after the host has
 //                  seen that no row index was out of range: such a call writes nothing)
 //   k_dist_small   one lane per pair: the sequential driver dist::distance (with the part kinds)
 //   k_dist_block   one workgroup per pair.  Containment first, one lane per (polygon part, component)
 //                  and direction; a component is a point, a line part or a polygon's shell, located
 //                  by its first vertex.  Then the side with fewer facets is staged in LDS, a tile of
-//                  dist_tile segments at a time, and the other side's segments are streamed across the
-//                  lanes, each lane keeping a running minimum.  The workgroup's current minimum lives
+//                  dist_tile segments at a time (pairs::stage_tile, pairs::tile_box), and the other side's
+//                  segments are streamed across the lanes, each lane keeping a running minimum (its own
+//                  loop: pairs::sweep_tiles prunes by boxes meeting).  The workgroup's current minimum lives
 //                  in LDS as the bit pattern of a non-negative double (integer atomicMin); a
 //                  (tile, streamed geometry), (tile, streamed ring) or (tile, streamed segment) block is
 //                  skipped only when dist::box_lower_bound of it is strictly greater than that minimum,
@@ -30,10 +32,9 @@
 //                  shuffles, then across the waves through LDS.
 #include <memory>
 
-#include "dev_rt.h"
 #include "geoms_build.h"
 #include "geoms_device.h"
-#include "pair_lists.h"
+#include "pair_call.h"
 #include "st_distance.h"
 
 using namespace mosaic;
@@ -42,12 +43,8 @@ namespace {
 
 using dev::blocks_for;
 using dev::Buf;
-using dev::is_device_ptr;
-using pairs::Col;
 using pairs::kBlock;
-using pairs::view;
-using pairs::wave_append;
-constexpr int kMaxTile = 1024;
+using pairs::kMaxTile;
 
 // a point column built on the device: row i is the point part (x[i], y[i]); a NaN coordinate is POINT EMPTY
 __global__ void __launch_bounds__(kBlock) k_points_col(const double* x, const double* y, int64_t n, pip::Vec2* verts,
@@ -77,44 +74,21 @@ __global__ void __launch_bounds__(kBlock) k_points_col(const double* x, const do
     }
 }
 
-struct PlanArgs {
-    Col L, R;
-    const int64_t *lrow, *rrow;  // both null: pair i is (row i, row i)
-    int64_t n;
-    unsigned long long small_work;
-    int32_t* plan;                 // the pair's status
-    int64_t* list;                 // small pairs from the front, block pairs from the back
-    unsigned long long* counts;    // [0] small, [1] block, [2] row indices out of range
-};
-
-__global__ void __launch_bounds__(kBlock) k_dist_plan(PlanArgs a) {
+__global__ void __launch_bounds__(kBlock) k_dist_plan(pairs::PlanArgs a) {
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < a.n; i0 += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = i0 + threadIdx.x;
         bool small = false, block = false;
         if (i < a.n) {
-            const int64_t g = a.lrow ? a.lrow[i] : i, h = a.rrow ? a.rrow[i] : i;
-            if (g < 0 || g >= a.L.n || h < 0 || h >= a.R.n) {
-                atomicAdd(&a.counts[2], 1ull);
-                a.plan[i] = -1;
-            } else {
-                const int32_t sl = a.L.status[g], sr = a.R.status[h];
-                int32_t st = MOSAIC_ROW_OK;
-                if (sl == MOSAIC_ROW_NULL || sr == MOSAIC_ROW_NULL)
-                    st = MOSAIC_ROW_NULL;
-                else if (sl != MOSAIC_ROW_OK || sr != MOSAIC_ROW_OK)
-                    st = MOSAIC_ROW_PATH;
-                a.plan[i] = st;
-                if (st == MOSAIC_ROW_OK) {
-                    const unsigned long long work = (unsigned long long)a.L.facets[g] * a.R.facets[h];
-                    small = work <= a.small_work;
-                    block = !small;
-                }
+            int64_t g, h;
+            const int32_t st = pairs::plan_status(a, i, g, h);
+            a.plan[i] = st;
+            if (st == MOSAIC_ROW_OK) {
+                const unsigned long long work = (unsigned long long)a.L.facets[g] * a.R.facets[h];
+                small = work <= a.small_work;
+                block = !small;
             }
         }
-        const unsigned long long ps = wave_append(&a.counts[0], small);
-        const unsigned long long pb = wave_append(&a.counts[1], block);
-        if (small) a.list[ps] = i;
-        if (block) a.list[a.n - 1 - (int64_t)pb] = i;
+        pairs::plan_append(a, i, small, block);
     }
 }
 
@@ -126,11 +100,7 @@ __global__ void __launch_bounds__(kBlock) k_dist_fill(const int32_t* plan, int64
     }
 }
 
-struct DistArgs {
-    Col L, R;
-    const int64_t *lrow, *rrow;
-    const int64_t* list;
-    int64_t n_list;
+struct DistArgs : pairs::ListArgs {
     double* out;
     int tile;
     int prune;
@@ -139,7 +109,8 @@ struct DistArgs {
 __global__ void __launch_bounds__(kBlock) k_dist_small(DistArgs a) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n_list; k += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = a.list[k];
-        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        uint32_t g, h;
+        pairs::pair_rows(a, i, g, h);
         a.out[i] = dist::distance(a.L.s, a.L.part_kind, g, a.R.s, a.R.part_kind, h);
     }
 }
@@ -158,11 +129,12 @@ __global__ void __launch_bounds__(kBlock) k_dist_block(DistArgs a) {
     const uint32_t T = (uint32_t)a.tile;
     for (int64_t k = blockIdx.x; k < a.n_list; k += gridDim.x) {
         const int64_t i = a.list[k];
-        const uint32_t g = (uint32_t)(a.lrow ? a.lrow[i] : i), h = (uint32_t)(a.rrow ? a.rrow[i] : i);
+        uint32_t g, h;
+        pairs::pair_rows(a, i, g, h);
         // S: the staged side (fewer facets), W: the streamed side; flip: S is the right geometry
         const bool flip = a.L.facets[g] > a.R.facets[h];
-        const Col& CS = flip ? a.R : a.L;
-        const Col& CW = flip ? a.L : a.R;
+        const pairs::Col& CS = flip ? a.R : a.L;
+        const pairs::Col& CW = flip ? a.L : a.R;
         const pip::GeomStore& S = CS.s;
         const pip::GeomStore& W = CW.s;
         const uint32_t gs = flip ? h : g, gw = flip ? g : h;
@@ -207,33 +179,14 @@ __global__ void __launch_bounds__(kBlock) k_dist_block(DistArgs a) {
             for (uint32_t f0 = 0; f0 < nf; f0 += T) {
                 const uint32_t cnt = nf - f0 < T ? nf - f0 : T;
                 __syncthreads();  // the previous tile's readers of s_v / s_box are done
-                for (uint32_t t = tid; t <= cnt; t += kBlock) {
-                    const uint32_t vi = f0 + t < n ? f0 + t : n - 1;
-                    s_v[t] = S.verts[v0 + vi];
-                }
+                pairs::stage_tile(s_v, S.verts + v0, n, f0, cnt);
                 if (tid == 0) s_snap = s_min;
                 __syncthreads();
                 if (s_snap == 0) {  // uniform: a zero ends the pair
                     done = true;
                     break;
                 }
-                if (tid < 64) {
-                    pip::Box b = {INFINITY, INFINITY, -INFINITY, -INFINITY};
-                    for (uint32_t t = tid; t <= cnt; t += 64) {
-                        const pip::Vec2 v = s_v[t];
-                        b.minx = fmin(b.minx, v.x);
-                        b.miny = fmin(b.miny, v.y);
-                        b.maxx = fmax(b.maxx, v.x);
-                        b.maxy = fmax(b.maxy, v.y);
-                    }
-                    for (int off = 32; off; off >>= 1) {
-                        b.minx = fmin(b.minx, __shfl_xor(b.minx, off, 64));
-                        b.miny = fmin(b.miny, __shfl_xor(b.miny, off, 64));
-                        b.maxx = fmax(b.maxx, __shfl_xor(b.maxx, off, 64));
-                        b.maxy = fmax(b.maxy, __shfl_xor(b.maxy, off, 64));
-                    }
-                    if (tid == 0) s_box = b;
-                }
+                pairs::tile_box(s_v, cnt, &s_box);
                 __syncthreads();
                 const pip::Box tb = s_box;
                 if (a.prune && dist::box_lower_bound(tb, wbox) > __longlong_as_double((long long)s_snap)) continue;  // uniform
@@ -246,11 +199,7 @@ __global__ void __launch_bounds__(kBlock) k_dist_block(DistArgs a) {
                         dist::ring_facet(W.verts + w0, nw, j, C, D);
                         const double cur = lds_min(&s_min);
                         if (cur == 0) break;
-                        if (a.prune) {
-                            const pip::Box sb = {C.x < D.x ? C.x : D.x, C.y < D.y ? C.y : D.y, C.x > D.x ? C.x : D.x,
-                                                 C.y > D.y ? C.y : D.y};
-                            if (dist::box_lower_bound(tb, sb) > cur) continue;
-                        }
+                        if (a.prune && dist::box_lower_bound(tb, dist::facet_box(C, D)) > cur) continue;
                         double mm = m;
                         if (flip) {
                             for (uint32_t t = 0; t < cnt; t++) mm = dist::min2(mm, dist::segment_segment(C, D, s_v[t], s_v[t + 1]));
@@ -421,74 +370,25 @@ int mosaic_geoms_destroy(mosaic_geoms* g) {
 
 int mosaic_st_distance(mosaic_ctx* ctx, const mosaic_geoms* left, const mosaic_geoms* right, const int64_t* left_row,
                        const int64_t* right_row, int64_t n_pairs, double* out, int32_t* status) {
-    if (!ctx || !left || !right || n_pairs < 0 || (n_pairs > 0 && !out))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
-    if ((left_row == nullptr) != (right_row == nullptr))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: left_row and right_row are both given or both null");
-    if (!left_row && (n_pairs > left->n_geoms || n_pairs > right->n_geoms))
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: row-wise form with more pairs than rows");
-    int tile = 16, prune = 1;
-    int64_t small_work = 512;
-    dev::Exec ex;
-    MOSAIC_RC(dev::enter(ctx, &ex));
-    MOSAIC_RC(mosaic_ctx_dist_options(ctx, &tile, &small_work, &prune));
-    if (left->device != ex.device || right->device != ex.device)
-        return mosaic_tess_fail(MOSAIC_E_ARG, "st_distance: a geometry column of another device");
+    pairs::Call<double> c;
+    MOSAIC_RC(c.open("st_distance", ctx, left, right, left_row, right_row, n_pairs, out));
     if (n_pairs == 0) return MOSAIC_OK;
-    tile = std::max(1, std::min(tile, kMaxTile));
-    hipStream_t stream = ex.stream;
-    const int64_t n = n_pairs;
-
-    Buf s_lrow, s_rrow, s_plan, s_list, s_counts, s_out, s_status;
-    PlanArgs pa{view(left), view(right), nullptr, nullptr, n, (unsigned long long)std::max<int64_t>(small_work, 0), nullptr, nullptr, nullptr};
-    if (left_row) {
-        MOSAIC_RC(dev::on_device(left_row, n, s_lrow, stream, &pa.lrow));
-        MOSAIC_RC(dev::on_device(right_row, n, s_rrow, stream, &pa.rrow));
-    }
-    MOSAIC_RC(s_plan.reserve((size_t)n * sizeof(int32_t)));
-    MOSAIC_RC(s_list.reserve((size_t)n * sizeof(int64_t)));
-    MOSAIC_RC(s_counts.reserve(4 * sizeof(unsigned long long)));
-    MOSAIC_HIP(hipMemsetAsync(s_counts.p, 0, 4 * sizeof(unsigned long long), stream));
-    pa.plan = (int32_t*)s_plan.p;
-    pa.list = (int64_t*)s_list.p;
-    pa.counts = (unsigned long long*)s_counts.p;
-    const int64_t wide = (int64_t)ex.n_cu * 16;
-    hipLaunchKernelGGL(k_dist_plan, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa);
+    MOSAIC_RC(c.stage(4));
+    hipLaunchKernelGGL(k_dist_plan, c.lanes(c.n), dim3(kBlock), 0, c.stream, c.pa);
     MOSAIC_HIP(hipGetLastError());
-    unsigned long long counts[4] = {0, 0, 0, 0};
-    MOSAIC_HIP(hipMemcpyAsync(counts, s_counts.p, sizeof(counts), hipMemcpyDeviceToHost, stream));
-    MOSAIC_HIP(hipStreamSynchronize(stream));
-    if (counts[2])
-        return mosaic_tess_fail(MOSAIC_E_ARG, ("st_distance: " + std::to_string(counts[2]) + " pair(s) name a row outside their column").c_str());
-
-    const bool dev_out = is_device_ptr(out), dev_status = !status || is_device_ptr(status);
-    double* d_out = out;
-    int32_t* d_status = status;
-    if (!dev_out) {
-        MOSAIC_RC(s_out.reserve((size_t)n * sizeof(double)));
-        d_out = (double*)s_out.p;
-    }
-    if (!dev_status) {
-        MOSAIC_RC(s_status.reserve((size_t)n * sizeof(int32_t)));
-        d_status = (int32_t*)s_status.p;
-    }
-    hipLaunchKernelGGL(k_dist_fill, dim3((unsigned)blocks_for(n, kBlock, wide)), dim3(kBlock), 0, stream, pa.plan, n, d_out, d_status);
+    MOSAIC_RC(c.planned());
+    MOSAIC_RC(c.bind(out, status));
+    hipLaunchKernelGGL(k_dist_fill, c.lanes(c.n), dim3(kBlock), 0, c.stream, c.pa.plan, c.n, c.out.dev, c.status.dev);
     MOSAIC_HIP(hipGetLastError());
-    DistArgs da{pa.L, pa.R, pa.lrow, pa.rrow, pa.list, (int64_t)counts[0], d_out, tile, prune};
-    if (counts[0]) {
-        hipLaunchKernelGGL(k_dist_small, dim3((unsigned)blocks_for((int64_t)counts[0], kBlock, wide)), dim3(kBlock), 0, stream, da);
+    if (c.n_small()) {
+        hipLaunchKernelGGL(k_dist_small, c.lanes(c.n_small()), dim3(kBlock), 0, c.stream, DistArgs{c.small_list(), c.out.dev, c.tile, c.prune});
         MOSAIC_HIP(hipGetLastError());
     }
-    if (counts[1]) {
-        da.list = pa.list + (n - (int64_t)counts[1]);
-        da.n_list = (int64_t)counts[1];
-        hipLaunchKernelGGL(k_dist_block, dim3((unsigned)std::min<int64_t>(da.n_list, (int64_t)1 << 20)), dim3(kBlock), 0, stream, da);
+    if (c.n_block()) {
+        hipLaunchKernelGGL(k_dist_block, c.groups(c.n_block()), dim3(kBlock), 0, c.stream, DistArgs{c.block_list(), c.out.dev, c.tile, c.prune});
         MOSAIC_HIP(hipGetLastError());
     }
-    if (!dev_out) MOSAIC_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (!dev_status) MOSAIC_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    MOSAIC_HIP(hipStreamSynchronize(stream));
-    return MOSAIC_OK;
+    return c.finish(false);
 }
 
 }  // extern "C"

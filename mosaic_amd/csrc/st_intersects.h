@@ -75,10 +75,6 @@ using pip::Box;
 using pip::GeomStore;
 using pip::Vec2;
 
-MOSAIC_HD Box facet_box(Vec2 a, Vec2 b) {
-    return Box{a.x < b.x ? a.x : b.x, a.y < b.y ? a.y : b.y, a.x > b.x ? a.x : b.x, a.y > b.y ? a.y : b.y};
-}
-
 // step 3: some facet of g meets some facet of h
 MOSAIC_HD bool facets_meet(const GeomStore& sa, uint32_t g, const GeomStore& sb, uint32_t h) {
     uint32_t ra0, ra1, rb0, rb1;

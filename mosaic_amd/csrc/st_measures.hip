@@ -27,7 +27,7 @@ namespace {
 
 using dev::blocks_for;
 using dev::Buf;
-using dev::is_device_ptr;
+using dev::OutSlot;
 using pairs::Col;
 using pairs::kBlock;
 using pairs::view;
@@ -198,29 +198,6 @@ __global__ void __launch_bounds__(64) k_meas_wave(MeasArgs a) {
         }
     }
 }
-
-// one output array: the caller's if it is on the device, else a staging block copied back at the end
-template <class T>
-struct OutSlot {
-    T* user = nullptr;
-    T* dev = nullptr;
-    Buf stage;
-    int bind(T* p, int64_t n) {
-        user = p;
-        if (!p) return MOSAIC_OK;
-        if (is_device_ptr(p)) {
-            dev = p;
-            return MOSAIC_OK;
-        }
-        MOSAIC_RC(stage.reserve((size_t)n * sizeof(T)));
-        dev = (T*)stage.p;
-        return MOSAIC_OK;
-    }
-    int back(int64_t n, hipStream_t stream) {
-        if (user && user != dev) MOSAIC_HIP(hipMemcpyAsync(user, dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
-        return MOSAIC_OK;
-    }
-};
 
 }  // namespace
 
