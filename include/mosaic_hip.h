@@ -423,6 +423,13 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
  * groups handed to the host, (cell, segment) pairs emitted; ms = device time (HIP events) of the walk
  * (spans included), the sort (grouping included) and the clip. */
 int mosaic_tess_lines_last(int64_t out[4], double ms[3]);
+/* The walk of the calling thread's last mosaic_tessellate_lines_gpu, read-only: out = spans walked (the
+ * sum of the segments' span counts), spans whose walk tried more than 64 cells and went to the host
+ * routine, (cell, segment) pairs those spans added (counted in mosaic_tess_lines_last's pairs, before
+ * equal pairs of overlapping spans are dropped).  All zero after a call without vertices; not specified
+ * after a call that failed.  The groups handed to the host are mosaic_tess_lines_last's out[2]:
+ * neither count includes the other. */
+int mosaic_tess_lines_last_walk(int64_t out[3]);
 
 /* ---- st_contains per row ---- */
 /* out[i] = JTS contains(geometry[geom_index[i]], POINT(px[i] py[i])); geometries given as WKB. */

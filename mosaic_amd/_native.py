@@ -48,7 +48,7 @@ EXPORTS = [
     "mosaic_geoms_create_points", "mosaic_geoms_info", "mosaic_geoms_destroy", "mosaic_st_distance",
     "mosaic_cell_index_create", "mosaic_cell_index_info", "mosaic_cell_index_destroy", "mosaic_ring_neighbours",
     "mosaic_neighbours_info", "mosaic_neighbours_export", "mosaic_neighbours_destroy", "mosaic_ring_neighbours_last_ms",
-    "mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last",
+    "mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last", "mosaic_tess_lines_last_walk",
     "mosaic_line_chips_create", "mosaic_line_chips_info", "mosaic_line_chips_destroy",
     "mosaic_line_intersects_aggregate", "mosaic_line_join_last", "mosaic_line_join_team",
     "mosaic_line_intersects_aggregate_host", "mosaic_geoms_create_wkb_ex", "mosaic_geoms_create_lines",
@@ -155,6 +155,7 @@ def lib():
         "mosaic_tessellate_lines": ([i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
         "mosaic_tessellate_lines_gpu": ([vp, i32, i32, i64, vp, vp, vp, i32, ctypes.POINTER(vp)], i32),
         "mosaic_tess_lines_last": ([vp, vp], i32),
+        "mosaic_tess_lines_last_walk": ([vp], i32),
         "mosaic_line_chips_create": ([vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, ctypes.POINTER(vp)], i32),
         "mosaic_line_chips_info": ([vp, vp], i32),
         "mosaic_line_chips_destroy": ([vp], i32),

@@ -40,6 +40,7 @@ using dev::Buf;
 
 struct Last {
     int64_t n[4] = {0, 0, 0, 0};
+    int64_t walk[3] = {0, 0, 0};  // spans walked, spans handed to the host routine, the pairs those added
     double ms[3] = {0, 0, 0};
 };
 thread_local Last g_last;
@@ -52,7 +53,9 @@ struct Batch {
     int64_t n_verts;
 };
 
-// counters[0]: the first segment that came to a bad cell (atomicMin); [1]: spans / groups for the host
+// counters[0]: the first segment that came to a bad cell (atomicMin; the host reads it after the walk has
+// added its own, so that a call names the first bad segment of the batch whichever stage finds it);
+// [1]: spans / groups for the host
 __global__ void __launch_bounds__(kBlock) k_line_spans(Batch b, int64_t* spans, unsigned long long* counters) {
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= b.n_verts; s += step) {
@@ -80,7 +83,7 @@ __device__ int64_t span_segment(const int64_t* span_off, int64_t n_verts, int64_
 
 // kWrite = false: counts span i's pairs and keeps the first kSlot of its cells in slot; kWrite = true (cnt
 // scanned): writes the pairs, from the slot where it holds them all, else by walking again.
-constexpr int kSlot = 8;
+using lineclip::kSlot;
 template <bool kWrite>
 __global__ void __launch_bounds__(kBlock) k_line_walk(Batch b, const int64_t* span_off, int64_t n_spans, int64_t* seen_all,
                                                       int64_t* cnt, uint8_t* status, unsigned long long* counters, uint64_t* slot,
@@ -189,6 +192,12 @@ int mosaic_tess_lines_last(int64_t out[4], double ms[3]) {
     return MOSAIC_OK;
 }
 
+int mosaic_tess_lines_last_walk(int64_t out[3]) {
+    if (!out) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
+    for (int i = 0; i < 3; i++) out[i] = g_last.walk[i];
+    return MOSAIC_OK;
+}
+
 int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_geoms, const int64_t* geom_lines,
                                 const int64_t* line_offsets, const double* xy, int cells_only, mosaic_chip_set** out) {
     if (!ctx || !out) return mosaic_tess_fail(MOSAIC_E_ARG, "invalid argument");
@@ -242,12 +251,14 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
     MOSAIC_RC(dev::exclusive_sum(d_tmp, d_spans.as<int64_t>(), d_spans.as<int64_t>(), (int)(nv + 1), st));  // in place: the last input is 0, the last sum the total
     int64_t n_spans = 0;
     MOSAIC_HIP(hipMemcpyAsync(&n_spans, d_spans.as<int64_t>() + nv, 8, hipMemcpyDeviceToHost, st));
-    MOSAIC_HIP(read_counters());
-    if (counters[0] != kNone) return linefill::fail_bad_cell(c, (int64_t)counters[0]);
+    MOSAIC_HIP(hipStreamSynchronize(st));
+    // (a segment whose span_count failed has no span and has put itself into counters[0], which is read
+    // after the walk's counting pass: an earlier segment may be bad for the walk alone)
     if (n_spans >= kMaxRows) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "line_fill: 2^31 - 1 spans at the most");
     int64_t n_segments = 0;
     for (int64_t l = 0; l < c.n_lines; l++) n_segments += std::max<int64_t>(0, c.line_off[(size_t)l + 1] - c.line_off[(size_t)l] - 1);
     g_last.n[0] = n_segments;
+    g_last.walk[0] = n_spans;
 
     // ---- walk: count, scan, write
     const unsigned walk_blocks = blocks_for(n_spans, kBlock, heavy);
@@ -265,10 +276,11 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
     int64_t n_dev_pairs = 0;
     MOSAIC_HIP(hipMemcpyAsync(&n_dev_pairs, d_cnt.as<int64_t>() + n_spans, 8, hipMemcpyDeviceToHost, st));
     MOSAIC_HIP(read_counters());
-    if (counters[0] != kNone) return linefill::fail_bad_cell(c, (int64_t)counters[0]);
-    // spans for the host
+    int64_t bad_seg = counters[0] == kNone ? -1 : (int64_t)counters[0];  // the first bad segment of both stages
+    // spans for the host (ascending, so by segment: one of an earlier segment than bad_seg may be bad too)
     std::vector<uint64_t> extra_cell;
     std::vector<uint32_t> extra_seg;
+    g_last.walk[1] = (int64_t)counters[1];
     if (counters[1]) {
         std::vector<uint8_t> status((size_t)n_spans);
         std::vector<int64_t> span_off((size_t)nv + 1);
@@ -279,15 +291,20 @@ int mosaic_tessellate_lines_gpu(mosaic_ctx* ctx, int grid, int res, int64_t n_ge
         for (int64_t i = 0; i < n_spans; i++) {
             if (status[(size_t)i] != lineclip::kNeedsMore) continue;
             const int64_t s = std::upper_bound(span_off.begin(), span_off.end(), i) - span_off.begin() - 1;
+            if (bad_seg >= 0 && s >= bad_seg) break;
             cells.clear();
             if (linefill::walk_span_host(G, c, s, (int32_t)(i - span_off[(size_t)s]), (int32_t)(span_off[(size_t)s + 1] - span_off[(size_t)s]),
-                                         cells) != lineclip::kOk)
-                return linefill::fail_bad_cell(c, s);
+                                         cells) != lineclip::kOk) {
+                bad_seg = s;
+                break;
+            }
             for (int64_t cell : cells) extra_cell.push_back((uint64_t)cell), extra_seg.push_back((uint32_t)s);
         }
         counters[1] = 0;
         MOSAIC_HIP(hipMemcpyAsync(d_counters.as<unsigned long long>() + 1, &counters[1], 8, hipMemcpyHostToDevice, st));
     }
+    if (bad_seg >= 0) return linefill::fail_bad_cell(c, bad_seg);
+    g_last.walk[2] = (int64_t)extra_cell.size();
     const int64_t n_pairs = n_dev_pairs + (int64_t)extra_cell.size();
     g_last.n[3] = n_pairs;
     if (n_pairs >= kMaxRows) return mosaic_tess_fail(MOSAIC_E_CAPACITY, "line_fill: 2^31 - 1 (cell, segment) pairs at the most");

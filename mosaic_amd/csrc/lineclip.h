@@ -45,6 +45,7 @@ using llclip::Pt;
 enum Status : int { kOk = 0, kNeedsMore = 1, kBadCell = 2 };
 
 static constexpr int kWalkCap = 64;  // device lane: cells one span's walk may try
+static constexpr int kSlot = 8;      // device lane: cells of one span the counting walk keeps for the writing pass
 static constexpr int kItems = 8;     // device lane: pieces (or isolated points) of one chip
 static constexpr int kMaxEvents = 34;  // boundary contacts of one segment: two per side at the most
 

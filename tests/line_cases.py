@@ -19,7 +19,9 @@ win over points (divergence (a)); the line is not noded at its own crossings (di
 component order, then the position (segment, parameter) where the chip begins, then the cell id.
 """
 import math
+import os
 import struct
+import subprocess
 
 import numpy as np
 
@@ -242,3 +244,106 @@ def item_count(blob):
     """Pieces (or isolated points) of a chip's WKB."""
     (t,) = struct.unpack(">I", blob[1:5])
     return struct.unpack(">I", blob[5:9])[0] if t in (4, 5) else 1
+
+
+# ---- inputs that reach the device walk's hand-off, its second walk and the error order ----
+# H3 cells are as wide in degrees of longitude as 1 / cos(lat): along a segment near a pole the spans,
+# sized by the start vertex's cell, come to cells several times narrower than themselves, and a walk
+# tries more than lineclip::kWalkCap cells.  No walk of these meets a cell that is no planar polygon.
+# (a, b, the spans span_count cuts a-b into)
+_POLAR = {
+    8: [((0.0, 89.9), (175.0, 89.5), 23)],
+    9: [((0.0, 89.9), (175.0, 89.5), 56), ((0.0, 89.9), (-175.0, 89.5), 56), ((10.0, 89.6), (175.0, 88.6), 153),
+        ((0.0, 89.0), (150.0, 86.5), 359)],
+    10: [((-170.0, 89.9), (0.0, 89.5), 145), ((0.0, 87.0), (170.0, 80.0), 3146)],
+}
+POLAR_SMALL_SPANS = 153  # segments of at most this many spans are cheap enough for the Python restatement
+
+
+def polar_segments(res, max_spans=None):
+    """(a, b, spans): high-latitude H3 segments of which at least one span's walk tries more than
+    kWalkCap cells; max_spans leaves out those cut into more spans."""
+    for a, b, k in _POLAR[res]:
+        if max_spans is None or k <= max_spans:
+            yield a, b, k
+
+
+def polar_batch(res):
+    """Every polar segment of the resolution as its own geometry, a MultiLineString of two polar
+    components (the first segment and the same reversed, which is cut into other spans) and an ordinary
+    line in New York."""
+    segs = [[a, b] for a, b, _ in polar_segments(res)]
+    return [[s] for s in segs] + [[segs[0], segs[0][::-1]], [[(-73.98, 40.75), (-73.95, 40.77), (-73.9, 40.8)]]]
+
+
+BNG_CORNER_DIAGONAL = [(400000.0, 300000.0), (410000.0, 310000.0)]  # resolution 4: through a lattice corner every 100 m
+
+
+def bng_corner_lines():
+    """The corner diagonal, three copies shifted by whole 100 m cells (every span of these emits more than
+    lineclip::kSlot cells: the line touches two diagonal cells at every corner) and one shifted by half a
+    cell, which passes through no corner."""
+    a, b = BNG_CORNER_DIAGONAL
+    shifts = [(0.0, 0.0), (300.0, 0.0), (0.0, 700.0), (-1100.0, 400.0), (50.0, 0.0)]
+    return [[[(a[0] + dx, a[1] + dy), (b[0] + dx, b[1] + dy)]] for dx, dy in shifts]
+
+
+# H3 resolution 5: the walk of A comes to a cell that is no planar polygon while span_count is fine with
+# it; B's span_count itself fails (its first vertex's cell holds the pole).
+ERROR_ORDINARY = [(-73.98, 40.75), (-73.9, 40.8)]
+ERROR_A = [(0.0, 89.8), (170.0, 89.0)]
+ERROR_B = [(0.0, 89.9), (175.0, 89.5)]
+
+
+def error_batches():
+    """Batches whose first bad geometry is number 1, found by the walk in one and by span_count in the other."""
+    return [[[ERROR_ORDINARY], [ERROR_A], [ERROR_B]], [[ERROR_ORDINARY], [ERROR_B], [ERROR_A]]]
+
+
+def segments_of(geoms):
+    """The segments (ax, ay, bx, by) both producers walk, in their order: cleaned lines, geometry by geometry."""
+    out = []
+    for lines in geoms:
+        for line in lines:
+            line = clean(line)
+            out += [(*a, *b) for a, b in zip(line, line[1:])]
+    return out
+
+
+def build_linewalk_caps(root, out_dir, sanitize=False):
+    """Compiles tests/native/linewalk_caps_host.cpp; the program's path."""
+    exe = os.path.join(str(out_dir), "linewalk_caps_san" if sanitize else "linewalk_caps")
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+    subprocess.run(["g++", *flags, "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I",
+                    os.path.join(root, "mosaic_amd", "csrc"), "-o", exe,
+                    os.path.join(root, "tests", "native", "linewalk_caps_host.cpp")], check=True)
+    return exe
+
+
+def walk_counts(exe, work_dir, grid, res, segments):
+    """tests/native/linewalk_caps_host.cpp over segments (ax, ay, bx, by): (caps, per segment (K, spans)) with
+    caps = dict(walk_cap, slot, items), K = -1 where span_count fails and spans = [(status, cells, bad)]."""
+    path = os.path.join(str(work_dir), "linewalk_caps.bin")
+    with open(path, "wb") as f:
+        np.array([0 if grid == H3 else 1, res, len(segments)], np.int64).tofile(f)
+        np.asarray(segments, np.float64).reshape(-1, 4).tofile(f)
+    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.splitlines()
+    head = out[0].split()
+    assert head[0] == "caps"
+    caps = dict(walk_cap=int(head[1]), slot=int(head[2]), items=int(head[3]))
+    segs = []
+    for ln in out[1:]:
+        t = ln.split()
+        if t[0] == "segment":
+            assert int(t[1]) == len(segs)
+            segs.append((int(t[2]), []))
+        else:
+            segs[-1][1].append((int(t[0]), int(t[1]), int(t[2])))
+    assert len(segs) == len(segments) and all(k < 0 or k == len(sp) for k, sp in segs)
+    return caps, segs
+
+
+def walk_totals(segs):
+    """Of walk_counts' segments: spans, spans that need more than kWalkCap tried cells, the cells those emit."""
+    spans = [sp for _, rows in segs for sp in rows]
+    return len(spans), sum(sp[0] == 1 for sp in spans), sum(sp[1] for sp in spans if sp[0] == 1)

@@ -213,7 +213,8 @@ def test_tessellate_dispatches_on_lineset_and_abi_stays():
     assert chips["is_core"].tolist() == [0] and chips["polygon_key"].tolist() == [0]
     assert chips["index_id"].tolist() == [cell_at(400500, 300500)]
     assert N.lib().mosaic_abi_version() == 4
-    for name in ("mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last"):
+    for name in ("mosaic_tessellate_lines", "mosaic_tessellate_lines_gpu", "mosaic_tess_lines_last",
+                 "mosaic_tess_lines_last_walk"):
         assert name in N.EXPORTS
 
 
@@ -261,3 +262,66 @@ def test_piece_builder_reports_needs_more_exactly(tmp_path, sanitize):
                     assert n == want and has_piece == int(got is not None and got[0] == "lines")
                 seen.add((more, want > 0, got is not None and got[0] == "points"))
     assert {(True, True, False), (False, True, False), (False, False, False), (True, True, True), (False, True, True)} <= seen
+
+
+# ---- inputs of the device walk's hand-off, its second walk and the error order (tests/test_gpu_line_fill.py) ----
+@pytest.fixture(scope="module")
+def walk_caps(tmp_path_factory):
+    """tests/native/linewalk_caps_host.cpp, compiled once, and once under ASan / UBSan for the small inputs:
+    walk_caps(grid, res, segments, checked=False) = (constants, per segment (K, spans))."""
+    d = tmp_path_factory.mktemp("linewalk")
+    plain, san = LC.build_linewalk_caps(ROOT, d), LC.build_linewalk_caps(ROOT, d, sanitize=True)
+
+    def run(grid, res, segments, checked=False):
+        got = LC.walk_counts(plain, d, grid, res, segments)
+        assert not checked or LC.walk_counts(san, d, grid, res, segments) == got
+        return got
+
+    return run
+
+
+@pytest.mark.parametrize("res", [8, 9])
+def test_polar_segments_equal_the_oracle(res):
+    geoms = [[[a, b]] for a, b, _ in LC.polar_segments(res, LC.POLAR_SMALL_SPANS)]
+    assert len(geoms) == {8: 1, 9: 3}[res]
+    got = host_rows("H3", geoms, res)
+    assert {r[0] for r in got} == set(range(len(geoms)))
+    assert got == LC.line_fill(LC.H3, res, geoms)
+
+
+@pytest.mark.parametrize("res", [8, 9, 10])
+def test_polar_segments_need_more_than_the_walk_cap(walk_caps, res):
+    """Pins that the inputs keep reaching the hand-off if a constant moves: every segment of the table has
+    a span whose walk tries more than kWalkCap cells, and no walk of the GPU tests' batch (which adds a
+    reversed segment and an ordinary line) meets a bad cell, so the host producer is a reference there."""
+    table = list(LC.polar_segments(res))
+    caps, segs = walk_caps(LC.H3, res, LC.segments_of(LC.polar_batch(res)), checked=res == 8)
+    assert caps == dict(walk_cap=64, slot=8, items=8)
+    assert all(k > 0 and not any(r[0] == 2 or r[2] for r in rows) and all(r[1] >= 1 for r in rows) for k, rows in segs)
+    for (a, b, spans), (k, rows) in zip(table, segs):
+        assert k == spans == len(rows)
+        assert sum(r[0] == 1 for r in rows) >= 1, (a, b)
+
+
+def test_bng_corner_diagonal_exceeds_the_slot_in_every_span(walk_caps):
+    lines = LC.bng_corner_lines()
+    caps, segs = walk_caps(LC.BNG, 4, LC.segments_of(lines), checked=True)
+    for k, rows in segs[:4]:
+        assert k == 50 and all(r[0] == 0 and not r[2] and caps["slot"] < r[1] <= caps["walk_cap"] for r in rows)
+    assert segs[4][0] == 50 and all(r[0] == 0 and not r[2] for r in segs[4][1])
+    # the suite's other BNG line has no such span
+    _, (long_one,) = walk_caps(LC.BNG, 4, [(380013.0, 290007.0, 415021.0, 309013.0)])
+    assert long_one[0] == 176 and max(r[1] for r in long_one[1]) <= caps["slot"]
+    got = host_rows("BNG", lines[:1] + lines[4:], 4)
+    assert got == LC.line_fill(LC.BNG, 4, lines[:1] + lines[4:])
+
+
+def test_error_batches_name_the_first_bad_geometry(walk_caps):
+    _, (fine, a, b) = walk_caps(LC.H3, 5, LC.segments_of([[LC.ERROR_ORDINARY], [LC.ERROR_A], [LC.ERROR_B]]), checked=True)
+    assert fine[0] >= 1 and not any(r[0] or r[2] for r in fine[1])
+    assert a[0] >= 1 and any(r[2] for r in a[1])  # span_count is fine with A; its walk meets a bad cell
+    assert b[0] == -1  # span_count fails
+    for geoms in LC.error_batches():
+        with pytest.raises(MosaicError) as e:
+            host_rows("H3", geoms, 5)
+        assert e.value.code == N.MOSAIC_E_ARG and str(e.value).startswith("geometry 1:")
